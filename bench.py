@@ -9,7 +9,18 @@ group is gloo (host): the gather, the barriers and the max-over-ranks timing run
 RCCL collective is on the data path (north_star: "tiles gathered on the host"). Total work is
 fixed: scaling = "strong". Rank 0 prints one JSON line.
 
-roofline (dominant kernel = the render megakernel; kernel_ms = its average device time per launch,
+A plain run does only what the headline figure needs: set-up, the warmup steps, the timed steps, the
+result line (metric, value, unit, ms_per_step, dtype, the workload's description). `--full` adds what
+costs runs or checks of its own: the untimed stats render (the path-vertex count), the frame digest, the
+roofline object and, at N = 1, the CPU baseline (`--no-cpu-baseline` leaves that one out).
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the last timed step delivered, the
+assembled RGB8 frame (height, width, 3), as DIR/frame_rgb.npy in float32. A frame above 48 MiB as
+float32 is written as a fixed sample instead: the (n, 3) pixels at the sorted flat pixel indices
+numpy.random.default_rng(0).choice(height * width, n, replace=False), the same at every run. Scene, seed
+and RNG are fixed by the arguments, so two builds can be compared value for value.
+
+roofline (--full; dominant kernel = the render megakernel; kernel_ms = its average device time per launch,
 HIP events recorded on the stream the kernel runs on). The megakernels keep every path in registers and
 read a scene of a few KB (cornell) from cache, so HBM does not bind them; f64 VALU issue does
 (the wait breakdown). The top-level fields therefore price the kernel against the FP64
@@ -40,7 +51,7 @@ cpu_baseline: the CPU oracle (a line-by-line f64 restatement of the reference's 
 reference itself is Rust and cannot be built here), compiled on this host with -O3 -march=native,
 on a bounded row band of the same frame on every core this job may use (host_cores(): the cgroup CPU
 quota, else the pool's declared share OMP_NUM_THREADS, else the affinity mask; os.cpu_count() is
-reported beside it), and on 1 thread; rank 0 at N = 1 only.
+reported beside it), and on 1 thread; rank 0 at N = 1 only, under --full.
 """
 import argparse
 import hashlib
@@ -81,7 +92,33 @@ def parse():
     ap.add_argument("--cpu-spp", type=int, default=256)
     ap.add_argument("--cpu-rows-1t", type=int, default=4, help="rows of the one-thread CPU sample")
     ap.add_argument("--partition", choices=["interleave", "stripes"], default="interleave")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the stats render (vertex count), the frame digest, the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame to DIR/frame_rgb.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_BYTES = 48 << 20  # of float32 values per dumped array (the whole dump stays below 64 MB)
+
+
+def dump_outputs(directory, frame):
+    """Writes the frame (rows, width, 3) u8 as directory/frame_rgb.npy in float32; a frame above DUMP_MAX_BYTES
+    as the fixed seeded sample of its pixels the module docstring describes."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    pixels = frame.reshape(-1, frame.shape[-1])
+    cap = DUMP_MAX_BYTES // (4 * pixels.shape[1])
+    if pixels.shape[0] > cap:
+        pixels = pixels[np.sort(np.random.default_rng(0).choice(pixels.shape[0], cap, replace=False))]
+        out = pixels.astype(np.float32)
+    else:
+        out = frame.astype(np.float32)
+    np.save(os.path.join(directory, "frame_rgb.npy"), out)
 
 
 def stripe(rank, world, height):
@@ -257,9 +294,39 @@ def roofline_block(mix, mix_source, vertices, samples, kernel_ms, traffic, traff
     return out
 
 
+def full_blocks(out, args, world, th, frame, st, total_vertices, n_samples, dev_ms, workload, mode):
+    """--full, rank 0: the frame digest and vertex counts (config), the roofline object and the CPU baseline
+    added to the result line `out`. th: this rank's rows; st: its stats render; dev_ms: its kernel time."""
+    import numpy as np
+
+    # the digest of the assembled frame is the same at every N
+    out["config"]["frame_sha1"] = hashlib.sha1(np.ascontiguousarray(frame).tobytes()).hexdigest()[:16]
+    out["config"]["vertices"] = total_vertices
+    out["config"]["vertices_per_sample"] = round(total_vertices / n_samples, 4)
+    rank_samples = args.width * th * 4 * (args.spp // 4)
+    kernel = "k_megakernel_f32" if args.fp32 else (
+        "k_megakernel_f64" if args.mode == "megakernel" else "k_wf_extend+k_wf_shade")
+    # traffic was measured at N = 1 on the whole frame: scale to this rank's share of the rows
+    traffic_full = load_profile("pmc_traffic.json", f"{workload} {mode}")
+    traffic = int(traffic_full * th / args.height) if traffic_full else None
+    npix = args.width * th
+    alg_bytes = npix * (2 * 12 * 8 + 3)  # f64 subpixel means written + read by the finalize, RGB8 out
+    # the instruction mix of this exact command (benchpmc); only the exact workload prices the roofline
+    mix_key = f"{workload} {mode}"
+    mix = load_profile("pmc_valu.json", mix_key) if args.mode == "megakernel" else None
+    out["roofline"] = roofline_block(
+        mix, f"profiles/pmc_valu.json[{mix_key!r}]", st["vertices"], rank_samples, dev_ms, traffic,
+        "profiles/pmc_traffic.json (2 x FETCH_SIZE + WRITE_SIZE per launch, rocprofv3 passes over this "
+        "command)", kernel, alg_bytes,
+        "valu_issue_f64" if args.mode == "megakernel" else "launches_and_state_traffic")
+    if mix:
+        out["roofline"]["compute"] = compute_block(mix, st["vertices"], dev_ms)
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args)
+
+
 def main():
     args = parse()
-    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -318,8 +385,9 @@ def main():
         pending[0] = buf
         last[0] = buf
 
-    # one untimed stats run: path-vertex count of this exact workload (device counter)
-    st = rt_amd.render_device(scene, params, rgb.data_ptr(), None, stream.cuda_stream, stats=True)
+    # --full: one untimed stats run, the path-vertex count of this exact workload (device counter)
+    st = rt_amd.render_device(scene, params, rgb.data_ptr(), None, stream.cuda_stream, stats=True) if args.full \
+        else None
     for i in range(args.warmup):
         step(i, False)
     flush()
@@ -335,14 +403,16 @@ def main():
         dist.barrier()
     wall = time.perf_counter() - t0
     dev_ms = sum(kernel_ms) / max(1, len(kernel_ms))
+    total_vertices = None  # --full only
     if world > 1:
         t = torch.tensor([wall], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
-        v = torch.tensor([st["vertices"]], dtype=torch.int64)
-        dist.all_reduce(v)
-        total_vertices = int(v.item())
-    else:
+        if args.full:
+            v = torch.tensor([st["vertices"]], dtype=torch.int64)
+            dist.all_reduce(v)
+            total_vertices = int(v.item())
+    elif args.full:
         total_vertices = st["vertices"]
 
     n_samples = args.width * args.height * 4 * (args.spp // 4)
@@ -350,22 +420,17 @@ def main():
     value = n_samples / (wall / args.steps) / 1e6
 
     if rank == 0:
-        # the frame: the gathered row sets put back in order; its digest is the same at every N
-        if world > 1:
-            frame = assemble([g.numpy() for g in gathered], world, args.height, args.partition)
-        else:
-            frame = last[0][:th].numpy()
-        digest = hashlib.sha1(np.ascontiguousarray(frame).tobytes()).hexdigest()[:16]
-        rank_samples = args.width * th * 4 * (args.spp // 4)
+        # the last timed step's frame: the gathered row sets put back in order
+        frame = None
+        if args.full or args.dump_outputs:
+            if world > 1:
+                frame = assemble([g.numpy() for g in gathered], world, args.height, args.partition)
+            else:
+                frame = last[0][:th].numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame)
         workload = f"{args.scene} {args.width}x{args.height}x{args.spp}spp{' mis' if args.mis else ''}"
         mode = args.mode + ("-f32" if args.fp32 else "")
-        kernel = "k_megakernel_f32" if args.fp32 else (
-            "k_megakernel_f64" if args.mode == "megakernel" else "k_wf_extend+k_wf_shade")
-        # traffic was measured at N = 1 on the whole frame: scale to this rank's share of the rows
-        traffic_full = load_profile("pmc_traffic.json", f"{workload} {mode}")
-        traffic = int(traffic_full * th / args.height) if traffic_full else None
-        npix = args.width * th
-        alg_bytes = npix * (2 * 12 * 8 + 3)  # f64 subpixel means written + read by the finalize, RGB8 out
         out = {
             "metric": "Msamples/sec (pixels x spp), cornell_box 1920x1080x1024spp" if args.scene == "cornell_box"
             and args.width == 1920 and args.height == 1080 and args.spp == 1024 and not args.fp32
@@ -387,24 +452,11 @@ def main():
                        "mode": mode, "mis": args.mis,
                        "parallelism": f"{'interleaved rows' if args.partition == 'interleave' else 'row stripes'} x{world}"
                                       ", host gather (gloo)" if world > 1 else "1 GPU",
-                       "frame_sha1": digest,
                        "device_map": f"every rank on GPU {device} (RT_BENCH_DEVICE: a rehearsal, timing not "
-                                     "meaningful)" if pinned not in (None, "") else "rank -> LOCAL_RANK",
-                       "vertices": total_vertices,
-                       "vertices_per_sample": round(total_vertices / n_samples, 4)},
+                                     "meaningful)" if pinned not in (None, "") else "rank -> LOCAL_RANK"},
         }
-        # the instruction mix of this exact command (benchpmc); only the exact workload prices the roofline
-        mix_key = f"{workload} {mode}"
-        mix = load_profile("pmc_valu.json", mix_key) if args.mode == "megakernel" else None
-        out["roofline"] = roofline_block(
-            mix, f"profiles/pmc_valu.json[{mix_key!r}]", st["vertices"], rank_samples, dev_ms, traffic,
-            "profiles/pmc_traffic.json (2 x FETCH_SIZE + WRITE_SIZE per launch, rocprofv3 passes over this "
-            "command)", kernel, alg_bytes,
-            "valu_issue_f64" if args.mode == "megakernel" else "launches_and_state_traffic")
-        if mix:
-            out["roofline"]["compute"] = compute_block(mix, st["vertices"], dev_ms)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args)
+        if args.full:
+            full_blocks(out, args, world, th, frame, st, total_vertices, n_samples, dev_ms, workload, mode)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,4 +1,4 @@
-"""The driver's N-rank bench path on the one GPU of the test box (bench.py:213-367; the reference's
+"""The driver's N-rank bench path on the one GPU of the test box (bench.py main(); the reference's
 row-band fan-out, server.rs:165-168): `torch.distributed.run --nproc-per-node 2 bench.py --gpus 2`, every
 rank mapped to GPU 0 by RT_BENCH_DEVICE=0 before any GPU call in the child. Each rank sets its device,
 joins the gloo group, renders its interleaved rows, copies them to pinned memory and gathers them on
@@ -14,7 +14,8 @@ import pytest
 
 from conftest import REPO
 
-ARGS = ["--steps", "1", "--warmup", "0", "--spp", "64", "--no-cpu-baseline"]
+# --full: the frame digest, the vertex count and the roofline object are in the full line only
+ARGS = ["--steps", "1", "--warmup", "0", "--spp", "64", "--full", "--no-cpu-baseline"]
 
 
 def _free_port():

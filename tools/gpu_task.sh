@@ -5,13 +5,13 @@
 #   tests            python -m pytest tests -m gpu (log: gpurun_out/$TAG/pytest_gpu.log)
 #   tests:EXPR       the same with -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (headline line, cpu_baseline included)
+#   bench            python bench.py --full (headline line, roofline and cpu_baseline included)
 #   rehearse[:N]     the N-rank bench path (default 2) on this one GPU: torchrun, every rank on GPU 0
 #                    (RT_BENCH_DEVICE=0), 1 step; its frame_sha1 must equal N = 1's
 #   trace            rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu-baseline`
 #   ktrace:SCRIPT[:ARGS]  rocprofv3 --kernel-trace --stats of `python SCRIPT ARGS` (":" separates args);
 #                    per-kernel totals -> $OUT/ktrace_<n>/run_kernel_stats.csv
-#   benchpmc         counter passes over `bench.py --steps 1 --warmup 0`: HBM bytes -> $OUT/pmc_traffic.json,
+#   benchpmc         counter passes over `bench.py --steps 1 --warmup 0 --full`: HBM bytes -> $OUT/pmc_traffic.json,
 #                    VALU mix + clock -> $OUT/pmc_valu.json (bench.py roofline.traffic / .compute)
 #   configs          tools/configs_bench.py (every BASELINE config, one GPU)
 #   pmc:SCENE:W:H:SPP[:mis]   counter passes on one megakernel render (tools/prof_render.py):
@@ -62,12 +62,12 @@ for task in "$@"; do
         timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || fail smoke "$OUT/smoke.log"
         tail -1 "$OUT/smoke.log" ;;
     bench)
-        timeout -k 10 600 python bench.py $BENCH_ARGS > "$OUT/bench.log" 2>&1 || fail bench "$OUT/bench.log"
+        timeout -k 10 600 python bench.py --full $BENCH_ARGS > "$OUT/bench.log" 2>&1 || fail bench "$OUT/bench.log"
         tail -1 "$OUT/bench.log" ;;
     rehearse)
         n=${A[1]:-2}
         RT_BENCH_DEVICE=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" \
-            --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$n" --steps 1 --warmup 0 $BENCH_ARGS \
+            --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$n" --steps 1 --warmup 0 --full $BENCH_ARGS \
             > "$OUT/rehearsal_n$n.log" 2>&1 || fail rehearse "$OUT/rehearsal_n$n.log"
         grep '^{"metric"' "$OUT/rehearsal_n$n.log" | tail -1 | cut -c1-400 ;;
     trace)
@@ -84,7 +84,7 @@ for task in "$@"; do
     benchpmc)
         # the bench command's own counters: HBM traffic (roofline.traffic; separate FETCH / WRITE passes)
         # and the VALU instruction mix + clock (roofline.compute), each pass a run of its own
-        B=(python bench.py --steps 1 --warmup 0 --no-cpu-baseline $BENCH_ARGS)
+        B=(python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline $BENCH_ARGS)
         pmc_pass bench_fetch FETCH_SIZE GRBM_GUI_ACTIVE -- "${B[@]}"
         pmc_pass bench_write WRITE_SIZE -- "${B[@]}"
         pmc_pass bench_sq1 $SQ1 -- "${B[@]}"

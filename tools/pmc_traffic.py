@@ -1,5 +1,5 @@
 """roofline.traffic for bench.py: HBM bytes per launch of the render kernel from the FETCH_SIZE and
-WRITE_SIZE passes (separate rocprofv3 runs of `bench.py --steps 1 --warmup 0 --no-cpu-baseline`,
+WRITE_SIZE passes (separate rocprofv3 runs of `bench.py --steps 1 --warmup 0 --full --no-cpu-baseline`,
 tools/gpu_task.sh benchpmc), merged into a JSON map {workload key: bytes}.
 
 usage: python tools/pmc_traffic.py <fetch run_counter_collection.csv> <write ...csv> <key> [kernel-substring]
