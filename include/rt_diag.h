@@ -7,10 +7,15 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* Device self-test of the exact-arithmetic shortcuts (path_f64.h: rcp_rn, qdiv, sqrt_rn) against
- * the IEEE operations on n pseudo-random operands on the current HIP device; writes min(n_out, 3)
- * counts: out[0] = reciprocal mismatches, out[1] = quotient mismatches, out[2] = square-root
- * mismatches (sqrt_rn's fast range [2^-767, 2^1024) against the library sqrt). Returns 0 or -1. */
+/* Device self-test of the exact-arithmetic shortcuts (path_f64.h: rcp_rn, qdiv, sqrt_rn, div_sqrt)
+ * against the IEEE operations on n pseudo-random operands on the current HIP device; writes
+ * min(n_out, 5) counts: out[0] = reciprocal mismatches, out[1] = quotient mismatches, out[2] =
+ * square-root mismatches (sqrt_rn's fast range [2^-767, 2^1024) against the library sqrt), out[3] =
+ * mismatches of the fused normalise div_sqrt(a, x) against a / sqrt(x) (library sqrt, IEEE division)
+ * over that range, out[4] = mismatches of div_sqrt, sqrt_rn, rcp_any and V3 / s against the library
+ * forms where every fourth wave holds one lane outside the fast ranges (0, subnormal, 2^-800, 2^+-1000,
+ * inf, NaN, negative) or at an edge of them (2^900 and its neighbours, around 2^-900 and 2^-767, the largest
+ * finite double); two NaNs are equal: a lane's bits do not depend on its wave-mates. Returns 0 or -1. */
 int rt_selftest_arith_n(long n, unsigned long long seed, unsigned long long* out, int n_out);
 /* The original entry point: out[0] reciprocal and out[1] quotient mismatches only. */
 int rt_selftest_arith(long n, unsigned long long seed, unsigned long long out[2]);

@@ -78,10 +78,11 @@ struct CameraSample {
     V3 d;
     uint64_t r0, r1;
 };
+template <bool G1 = false>
 RT_DEV CameraSample camera_sample(const DevScene& sc, const RenderArgs& a, const SubPixel& sp, int smp) {
     Rng rng(a.seed, sp.pid, (uint32_t)smp, (uint32_t)sp.sub);
     double u1 = rng.uniform(), u2 = rng.uniform();
-    const Ray r = camera_ray(sc, ld3(a.cx), ld3(a.cy), (double)a.width, (double)a.height, sp.col, sp.yref, sp.sx, sp.sy,
+    const Ray r = camera_ray<G1>(sc, ld3(a.cx), ld3(a.cy), (double)a.width, (double)a.height, sp.col, sp.yref, sp.sx, sp.sy,
                              u1, u2);
     return CameraSample{r.d, rng.s0, rng.s1};
 }
@@ -214,7 +215,7 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
         V3 f = brdf_eval<C>(obj, nrm, o, i);
         cold.set_bemit(ps, ps.beta);
         cold.set_o(ps, o);
-        ps.beta = mult(ps.beta, f) * dot(nrm, i) / (pdf * p);
+        ps.beta = vdiv<C::g1>(mult(ps.beta, f) * dot(nrm, i), pdf * p);
         ps.ray = Ray{x, i};
         ps.kind = K_SPEC;
         return true;
@@ -234,10 +235,10 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
 #if RT_OPT_VIS
         // norm(y - x) and |y - x| exactly as mutually_visible computes them (scene.rs:258-262): the
         // shadow ray reuses them
-        const double dist = sqrt_rn(r_sqr);  // == mag(diff)
-        const V3 i = diff / dist;          // == norm(diff)
+        double dist;                                 // == mag(diff)
+        const V3 i = div_sqrt<C::g1>(diff, r_sqr, &dist);  // == norm(diff), one vote (path_f64.h)
 #else
-        const V3 i = norm(diff);
+        const V3 i = norm<C::g1>(diff);
 #endif
         // Le * f: for a diffuse vertex Le_light * (kd / pi), evaluated once per object on the host
         // (mirror vertices have no NEE)
@@ -250,8 +251,8 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
 #if RT_OPT_VIS
             const Ray sr{x, i};
 #else
-            const double dist = mag(diff);
-            const Ray sr{x, diff / dist};
+            const double dist = mag<C::g1>(diff);
+            const Ray sr{x, vdiv<C::g1>(diff, dist)};
 #endif
             if constexpr (C::mesh && C::compact) {
                 if (defer) {
@@ -261,7 +262,7 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
 #if RT_NEAR32
                     const RayInv ninv{};  // near_cull32 takes its own f32 reciprocals
 #else
-                    const RayInv ninv = make_inv(sr.d);
+                    const RayInv ninv = make_inv<C::g1>(sr.d);
 #endif
                     const uint32_t near = vis > 0. ? mesh_near_mask<C>(sc, sr, ninv, dist) : 0u;
                     if (near) {
@@ -270,7 +271,7 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
                         if constexpr (Sink::lds) {
                             sink.put(sr.o, sr.d, dist);
                         } else {
-                            defer->inv = make_inv(sr.d);
+                            defer->inv = make_inv<C::g1>(sr.d);
                             defer->o = sr.o;
                             defer->d = sr.d;
                             defer->dist = dist;
@@ -288,9 +289,9 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
             if (!use_mis) {
 #if RT_OPT_NEE
                 // one scalar weight, one reciprocal (magnitude only: the same value up to the last bits)
-                c = lef * (vis * dot(nrm, i) * dot(ny, -i) * rcp_any(r_sqr * pdfA));
+                c = lef * (vis * dot(nrm, i) * dot(ny, -i) * rcp_any<C::g1>(r_sqr * pdfA));
 #else
-                c = lef * vis * dot(nrm, i) * dot(ny, -i) / (r_sqr * pdfA);
+                c = vdiv<C::g1>(lef * vis * dot(nrm, i) * dot(ny, -i), r_sqr * pdfA);
 #endif
             } else {
                 double cosl = dot(ny, -i);
@@ -299,7 +300,7 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
                 c = v3(0, 0, 0);
 #if RT_OPT_NEE
                 // (pdf_l / (pdf_l + pdf_b)) / pdf_l == 1 / (pdf_l + pdf_b)
-                if (vis > 0. && cosl > 0. && pdf_b > 0.) c = lef * (dot(nrm, i) * rcp_any(pdf_l + pdf_b));
+                if (vis > 0. && cosl > 0. && pdf_b > 0.) c = lef * (dot(nrm, i) * rcp_any<C::g1>(pdf_l + pdf_b));
 #else
                 if (vis > 0. && cosl > 0. && pdf_b > 0.) c = lef * dot(nrm, i) * ((pdf_l / (pdf_l + pdf_b)) / pdf_l);
 #endif
@@ -336,11 +337,11 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
     if ((!C::phong || obj.brdf != BRDF_PHONG) && cw != 0.0) {
         ps.beta = mult(ps.beta, ld3(obj.k)) * (ps.depth <= (uint32_t)MAX_BOUNCES ? 1.0 : kInvSurvival);
     } else {
-        ps.beta = mult(ps.beta, brdf_eval<C>(obj, nrm, o, wi)) * cw / (pdf * p);
+        ps.beta = vdiv<C::g1>(mult(ps.beta, brdf_eval<C>(obj, nrm, o, wi)) * cw, pdf * p);
     }
 #else
     V3 f = brdf_eval<C>(obj, nrm, o, wi);
-    ps.beta = mult(ps.beta, f) * dot(nrm, wi) / (pdf * p);
+    ps.beta = vdiv<C::g1>(mult(ps.beta, f) * dot(nrm, wi), pdf * p);
 #endif
     ps.ray = Ray{x, wi};
     ps.kind = spec ? K_SPEC : K_DIFF;

@@ -38,8 +38,15 @@ RT_DEV V3 operator*(double s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
 // [2^-900, 2^900]; otherwise, and for NaN/inf, the plain IEEE division is taken. The sign of a
 // zero quotient is restored from q0 (see qdiv). Bit-identical to a / b for finite a.
 #ifndef RT_OPT_VOTE
-#define RT_OPT_VOTE 1
+#define RT_OPT_VOTE 2  // A/B: the guards' wave votes as a scalar AND of single-compare ballots (2), as one
+                       // ballot of the conjunction (1: its boolean goes through a VGPR), or __all (0)
 #endif
+#ifndef RT_OPT_NORM1
+#define RT_OPT_NORM1 1  // A/B: a / sqrt(x) behind the square root's vote alone (div_sqrt) (1), or two votes (0)
+#endif
+#ifndef RT_OPT_GUARDI
+#define RT_OPT_GUARDI 1  // A/B: the range guards as unsigned window tests on the high dword (1), f64 compares (0)
+#endif                   // (cornell 1024 spp: votes 2004.6 -> 2093.7, windows 2103.1, profiles/r07_ab_guards.log)
 RT_DEV bool rcp_safe(double b) { return fabs(b) >= 0x1p-900 && fabs(b) <= 0x1p900; }
 // All active lanes satisfy p (a wave vote kept in SGPRs: ballot vs exec, no VGPR round trip).
 RT_DEV bool wave_all(bool p) {
@@ -48,6 +55,41 @@ RT_DEV bool wave_all(bool p) {
 #else
     return __all(p);
 #endif
+}
+// The guards' votes. A ballot folds into its compare (v_cmp writes the lane mask) only when its argument is
+// one compare; the ballot of a conjunction first materialises the boolean in a VGPR (v_cndmask 0/1, v_cmp_ne:
+// two VALU and a hazard nop per guard). So each range end is a ballot of its own and the masks meet on the
+// scalar side: (ballot(x >= lo) & ballot(x <= hi)) == exec. The same predicate, lane for lane (a NaN fails
+// both forms). RT_OPT_GUARDI makes each range one unsigned window test on the operand's high dword (sign,
+// exponent, top of the mantissa: 32-bit VALU instead of f64 compares, one ballot per operand); the windows
+// hold the same operands, or fewer (rcp: 2^900 itself is left out), so a fast path runs only where it did.
+RT_DEV uint64_t vote(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+RT_DEV bool vote_all(uint64_t m) { return m == __builtin_amdgcn_read_exec(); }
+RT_DEV uint32_t hi_dword(double x) { return (uint32_t)((uint64_t)__double_as_longlong(x) >> 32); }
+// lanes with |b| in rcp_rn's range [2^-900, 2^900] (RT_OPT_GUARDI: [2^-900, 2^900), a subset: biased
+// exponents 123 .. 1922, one unsigned window on the sign-stripped high dword)
+RT_DEV uint64_t rcp_vote(double b) {
+#if RT_OPT_GUARDI
+    return vote(((hi_dword(b) & 0x7FFFFFFFu) - 0x07B00000u) < 0x70800000u);
+#else
+    return vote(fabs(b) >= 0x1p-900) & vote(fabs(b) <= 0x1p900);
+#endif
+}
+// G1 (Cfg::g1, every guarded helper's template flag): the guards as they were before RT_OPT_VOTE=2 /
+// RT_OPT_NORM1 / RT_OPT_GUARDI, one ballot of the conjunction and two votes per normalise. The fused mesh
+// instances k_megakernel_f64<odd, 3> keep them: they run at their 168-VGPR cap with 150-260 spilled VGPRs, and
+// the new forms, cheaper in instructions, moved their spill counts up in six of eight instances (as
+// walk_step's Hoist flag keeps its hoist out of the instances it costs registers).
+constexpr bool kGuardsNew = RT_OPT_VOTE >= 2;
+template <bool G1 = false>
+RT_DEV bool rcp_safe_all(double b) {
+    if constexpr (kGuardsNew && !G1) return vote_all(rcp_vote(b));
+    else return wave_all(rcp_safe(b));
+}
+template <bool G1 = false>
+RT_DEV bool rcp_safe_all(double a, double b, double c) {
+    if constexpr (kGuardsNew && !G1) return vote_all(rcp_vote(a) & rcp_vote(b) & rcp_vote(c));
+    else return wave_all(rcp_safe(a) && rcp_safe(b) && rcp_safe(c));
 }
 // RN(1 / b) for rcp_safe(b): the compiler's own IEEE f64 division sequence for 1.0 / b (v_rcp_f64,
 // two Newton steps, residual correction) without its range scaling (v_div_scale) and special-case
@@ -63,8 +105,9 @@ RT_DEV double rcp_rn(double b) {
     return fma(e, r, r);
 }
 // 1 / b for any b: rcp_rn's sequence when every lane of the wave is in its range, else the library's
+template <bool G1 = false>
 RT_DEV double rcp_any(double b) {
-    if (wave_all(rcp_safe(b))) return rcp_rn(b);
+    if (rcp_safe_all<G1>(b)) return rcp_rn(b);
     return 1.0 / b;
 }
 #ifndef RT_OPT_QDIV
@@ -82,13 +125,15 @@ RT_DEV double qdiv(double a, double b, double y) {
     return r == 0.0 ? q0 : fma(r, y, q0);
 #endif
 }
-RT_DEV V3 operator/(V3 a, double s) {
-    if (wave_all(rcp_safe(s))) {  // wave-uniform: no per-lane exec juggling on the common path
+template <bool G1 = false>
+RT_DEV V3 vdiv(V3 a, double s) {
+    if (rcp_safe_all<G1>(s)) {  // wave-uniform: no per-lane exec juggling on the common path
         double y = rcp_rn(s);
         return v3(qdiv(a.x, s, y), qdiv(a.y, s, y), qdiv(a.z, s, y));
     }
     return v3(a.x / s, a.y / s, a.z / s);
 }
+RT_DEV V3 operator/(V3 a, double s) { return vdiv(a, s); }
 #ifndef RT_OPT_SQRT
 #define RT_OPT_SQRT 1  // A/B: unscaled sqrt sequence behind a wave vote (1) or the library sqrt (0)
 #endif
@@ -96,27 +141,74 @@ RT_DEV V3 operator/(V3 a, double s) {
 // Goldschmidt step and two Newton corrections) without its input scaling (an identity in that
 // range: ldexp by 0) and its 0/inf fixup (unreachable there); 11 VALU instead of 17. Other inputs
 // (0, tiny, inf, NaN, negative) take the library sqrt.
+RT_DEV double sqrt_fast(double x) {  // x in [2^-767, inf)
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = y * 0.5;
+    const double r = fma(-h, g, 0.5);
+    g = fma(g, r, g);
+    h = fma(h, r, h);
+    double d = fma(-g, g, x);
+    g = fma(d, h, g);
+    d = fma(-g, g, x);
+    return fma(d, h, g);
+}
+// every lane's x is in sqrt_fast's range (RT_OPT_GUARDI: the same set as one unsigned window on the high
+// dword, biased exponents 256 .. 2046 with the sign bit clear)
+template <bool G1 = false>
+RT_DEV bool sqrt_fast_all(double x) {
+    if constexpr (kGuardsNew && !G1) {
+#if RT_OPT_GUARDI
+        return vote_all(vote((hi_dword(x) - 0x10000000u) < 0x6FF00000u));
+#else
+        return vote_all(vote(x >= 0x1p-767) & vote(x < INFINITY));
+#endif
+    } else {
+        return wave_all(x >= 0x1p-767 && x < INFINITY);
+    }
+}
+template <bool G1 = false>
 RT_DEV double sqrt_rn(double x) {
 #if RT_OPT_SQRT
-    if (wave_all(x >= 0x1p-767 && x < INFINITY)) {
-        const double y = __builtin_amdgcn_rsq(x);
-        double g = x * y, h = y * 0.5;
-        const double r = fma(-h, g, 0.5);
-        g = fma(g, r, g);
-        h = fma(h, r, h);
-        double d = fma(-g, g, x);
-        g = fma(d, h, g);
-        d = fma(-g, g, x);
-        return fma(d, h, g);
-    }
+    if (sqrt_fast_all<G1>(x)) return sqrt_fast(x);
 #endif
     return sqrt(x);
+}
+// a / sqrt(x) and *root = sqrt(x), bit for bit `s = sqrt(x); a / s` in IEEE arithmetic, behind the square
+// root's vote alone. Range argument: a finite x >= 2^-767 has sqrt(x) in [2^-383.5, 2^512), inside rcp_rn's
+// [2^-900, 2^900], so where sqrt_rn's vote passes the division's vote on the root cannot fail and is not
+// taken. Where it fails (a lane with 0, a tiny, negative, infinite or NaN radicand) the whole wave takes the
+// library sqrt and IEEE divisions (with two votes such a wave could still divide through qdiv when every root
+// was in range: the same bits for finite a, where qdiv is the IEEE quotient). Precondition for that
+// neutrality: a is finite wherever sqrt(x) is in rcp_rn's range. It holds at every call site, where x is a's
+// own squared length (a non-finite a gives a non-finite x); a caller passing an unrelated x must keep it.
+template <bool G1 = false>
+RT_DEV V3 div_sqrt(V3 a, double x, double* root) {
+    if constexpr (RT_OPT_NORM1 && RT_OPT_SQRT && !G1) {
+        if (sqrt_fast_all(x)) {
+            const double s = sqrt_fast(x);
+            const double y = rcp_rn(s);
+            *root = s;
+            return v3(qdiv(a.x, s, y), qdiv(a.y, s, y), qdiv(a.z, s, y));
+        }
+        const double s = sqrt(x);
+        *root = s;
+        return v3(a.x / s, a.y / s, a.z / s);
+    } else {
+        const double s = sqrt_rn<G1>(x);
+        *root = s;
+        return vdiv<G1>(a, s);
+    }
 }
 RT_DEV double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 RT_DEV V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 RT_DEV V3 mult(V3 a, V3 b) { return v3(a.x * b.x, a.y * b.y, a.z * b.z); }
-RT_DEV double mag(V3 a) { return sqrt_rn(a.x * a.x + a.y * a.y + a.z * a.z); }
-RT_DEV V3 norm(V3 a) { return a / mag(a); }
+template <bool G1 = false>
+RT_DEV double mag(V3 a) { return sqrt_rn<G1>(a.x * a.x + a.y * a.y + a.z * a.z); }
+template <bool G1 = false>
+RT_DEV V3 norm(V3 a) {
+    double m;
+    return div_sqrt<G1>(a, a.x * a.x + a.y * a.y + a.z * a.z, &m);  // a / mag(a)
+}
 RT_DEV bool equal_within(V3 a, V3 b, double e) {
     return fabs(a.x - b.x) < e && fabs(a.y - b.y) < e && fabs(a.z - b.z) < e;
 }
@@ -186,9 +278,10 @@ RT_DEV V3 eval(const Ray& r, double t) { return r.o + t * r.d; }
 struct RayInv {
     double rx, ry, rz;
 };
+template <bool G1 = false>
 RT_DEV RayInv make_inv(const V3& d) {
     RayInv v;
-    if (wave_all(rcp_safe(d.x) && rcp_safe(d.y) && rcp_safe(d.z))) {  // wave-uniform fast path
+    if (rcp_safe_all<G1>(d.x, d.y, d.z)) {  // wave-uniform fast path
         v.rx = rcp_rn(d.x);
         v.ry = rcp_rn(d.y);
         v.rz = rcp_rn(d.z);
@@ -288,13 +381,14 @@ constexpr uint64_t kP53Survive = (uint64_t)(SURVIVAL_PROBABILITY * 9007199254740
 static_assert((double)kP53Survive == SURVIVAL_PROBABILITY * 9007199254740992.0, "0.9 * 2^53 must be an integer");
 
 // ---------------------------------------------------------------- primitives (geometry.rs:512-571)
+template <bool G1 = false>
 RT_DEV bool sphere_t(const DevObject& o, const Ray& ray, double* tout) {
     V3 op = ld3(o.pos) - ray.o;
     const double eps = 1e-4;
     double b = dot(op, ray.d);
     double det = b * b - dot(op, op) + o.r * o.r;
     if (det < 0.) return false;
-    det = sqrt_rn(det);
+    det = sqrt_rn<G1>(det);
     double t = b - det;
     if (t > eps) { *tout = t; return true; }
     t = b + det;
@@ -325,27 +419,22 @@ RT_DEV bool plane_t(const DevObject& o, const Ray& ray, const RayInv& inv, doubl
 // address space (flat_query reads its triangles through a constant-address-space pointer: s_load).
 // The triangle's unit normal: stored (DevTri), or recomputed for a 72-B leaf copy with the host's own
 // operations (rt_api.cpp: Triangle::normal = (c - a).cross(b - a).norm()), so the same bits.
-template <class TR>
+template <bool G1 = false, class TR>
 RT_DEV V3 tri_normal(const TR& tr) {
     if constexpr (sizeof(TR) == sizeof(DevTri)) {
         return ld3(tr.n);
     } else {
         const V3 ab = ld3(tr.ab), ac = ld3(tr.ac);
         const V3 cr = v3(ac.y * ab.z - ac.z * ab.y, ac.z * ab.x - ac.x * ab.z, ac.x * ab.y - ac.y * ab.x);
-        const double mg = sqrt_rn(cr.x * cr.x + cr.y * cr.y + cr.z * cr.z);
-        if (wave_all(rcp_safe(mg))) {
-            const double y = rcp_rn(mg);
-            return v3(qdiv(cr.x, mg, y), qdiv(cr.y, mg, y), qdiv(cr.z, mg, y));
-        }
-        return v3(cr.x / mg, cr.y / mg, cr.z / mg);
+        return norm<G1>(cr);
     }
 }
 #ifndef RT_TRI_MINORS
 #define RT_TRI_MINORS 1  // tri_t's determinants through their shared minors (1), or four det3 calls (0: A/B)
 #endif
-template <class TR>
+template <bool G1 = false, class TR>
 RT_DEV bool tri_t(const TR& tr, const Ray& ray, double* tout) {
-    V3 n = tri_normal(tr);
+    V3 n = tri_normal<G1>(tr);
     if (fabs(dot(n, ray.d)) < 0.0001) return false;
     V3 ab = ld3(tr.ab), ac = ld3(tr.ac);
     V3 b = ray.o - ld3(tr.a);
@@ -365,7 +454,7 @@ RT_DEV bool tri_t(const TR& tr, const Ray& ray, double* tout) {
     double tn = det3(b, ab, ac), un = det3(nd, b, ac), vn = det3(nd, ab, b);
 #endif
     double t, u, v;
-    if (wave_all(rcp_safe(det))) {  // wave-uniform
+    if (rcp_safe_all<G1>(det)) {  // wave-uniform
         double y = rcp_rn(det);
         t = qdiv(tn, det, y);
         u = qdiv(un, det, y);
@@ -764,6 +853,7 @@ constexpr int kTrisPerStep = RT_TRIS_PER_STEP;
 #ifndef RT_TRI_PRELOAD
 #define RT_TRI_PRELOAD 1  // A/B: the step's triangles are loaded whole before any test (1), or by tri_t (0)
 #endif
+template <bool G1 = false>
 RT_DEV int leaf_tris(const DevScene& sc, const Ray& ray, OctWalk& w, double* t, int* prim) {
 #if RT_TRI_PRELOAD
     // All of the step's triangles (96 B each) are loaded up front: tri_t reads a triangle's normal,
@@ -787,14 +877,14 @@ RT_DEV int leaf_tris(const DevScene& sc, const Ray& ray, OctWalk& w, double* t, 
             RT_DBG(4);
             double tt;
 #if RT_TRI_PRELOAD
-            if (tri_t(tr[j], ray, &tt) && (w.best < 0 || tt < w.bt)) {
+            if (tri_t<G1>(tr[j], ray, &tt) && (w.best < 0 || tt < w.bt)) {
 #else
 #if RT_LTRI_INDEX
             const DevTri& trj = sc.tris[sc.ltri_id[w.lpos]];  // leaf list = triangle indices (3.6 MB table)
 #else
             const LeafTri& trj = sc.ltris[w.lpos];  // leaf list = triangle copies (18 MB for the unicorn)
 #endif
-            if (tri_t(trj, ray, &tt) && (w.best < 0 || tt < w.bt)) {
+            if (tri_t<G1>(trj, ray, &tt) && (w.best < 0 || tt < w.bt)) {
 #endif
                 w.bt = tt;
                 w.best = w.lpos;
@@ -813,6 +903,7 @@ RT_DEV int leaf_tris(const DevScene& sc, const Ray& ray, OctWalk& w, double* t, 
 // The tests of leaf_tris on triangles already loaded (the slot walk's hoisted loads, walk_step<true>).
 // tid (RT_LTRI_ID_HOIST): the triangles' global ids, loaded with them; w.best then holds the best
 // triangle's id itself, so a hit needs no dependent ltri_id load at the leaf's end.
+template <bool G1 = false>
 RT_DEV int leaf_tris_loaded(const DevScene& sc, const Ray& ray, OctWalk& w, const LeafTri* tr, double* t, int* prim,
                             const int32_t* tid = nullptr) {
 #pragma unroll
@@ -820,7 +911,7 @@ RT_DEV int leaf_tris_loaded(const DevScene& sc, const Ray& ray, OctWalk& w, cons
         if (w.lpos < w.lend) {
             RT_DBG(4);
             double tt;
-            if (tri_t(tr[j], ray, &tt) && (w.best < 0 || tt < w.bt)) {
+            if (tri_t<G1>(tr[j], ray, &tt) && (w.best < 0 || tt < w.bt)) {
                 w.bt = tt;
                 w.best = tid ? tid[j] : w.lpos;
             }
@@ -1248,7 +1339,7 @@ RT_DEV int walk_node(const DevScene& sc, const DevMesh& m, const Ray& ray, const
 // walk inlined there trips an AMDGPU backend error, "illegal VGPR to SGPR copy", in ROCm 7.2.)
 // Hoist: RT_WALK_HOIST's modes (below); the Phong / mesh-light instances of the walk pool pass 0, where
 // the hoisted triangles' registers would spill.
-template <bool Slots = (RT_WALK_TIGHT != 0), int AS = 256, int Hoist = RT_WALK_HOIST, class Anc = LdsAncI32>
+template <bool Slots = (RT_WALK_TIGHT != 0), int AS = 256, int Hoist = RT_WALK_HOIST, class Anc = LdsAncI32, bool G1 = false>
 RT_DEV int walk_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const RayInv& inv, OctWalk& w, double* t,
                      int* prim, Anc* anc = nullptr) {
     RT_DBG(5);
@@ -1291,8 +1382,8 @@ RT_DEV int walk_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const
         }
         RT_DBG_TSTART(t_lt);
         if (Hoist != 0 ? open : w.lpos < w.lend) {
-            const int st = Hoist != 0 ? leaf_tris_loaded(sc, ray, w, tr, t, prim, (RT_LTRI_ID_HOIST || RT_LTRI_INDEX) ? tid : nullptr)
-                                      : leaf_tris(sc, ray, w, t, prim);
+            const int st = Hoist != 0 ? leaf_tris_loaded<G1>(sc, ray, w, tr, t, prim, (RT_LTRI_ID_HOIST || RT_LTRI_INDEX) ? tid : nullptr)
+                                      : leaf_tris<G1>(sc, ray, w, t, prim);
             if (st == WALK_HIT) {
                 RT_DBG_TEND(12, t_lt);
                 return WALK_HIT;
@@ -1312,14 +1403,14 @@ RT_DEV int walk_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const
     }
     int st = -1;
     RT_DBG_TSTART(t_lt);
-    if (w.lpos < w.lend) st = leaf_tris(sc, ray, w, t, prim);  // triangles of the open leaf
+    if (w.lpos < w.lend) st = leaf_tris<G1>(sc, ray, w, t, prim);  // triangles of the open leaf
     RT_DBG_TEND(12, t_lt);
     if (st >= 0) return st;
     (void)anc;
     st = walk_node(sc, m, ray, inv, w);
 #if RT_WALK_OPEN_TEST
     if (st == WALK_RUN && w.lpos < w.lend) {  // a leaf was just opened: its first triangles in this step
-        const int s2 = leaf_tris(sc, ray, w, t, prim);
+        const int s2 = leaf_tris<G1>(sc, ray, w, t, prim);
         return s2 >= 0 ? s2 : WALK_RUN;
     }
 #endif
@@ -1346,7 +1437,7 @@ RT_DEV void bvh_begin(const DevMesh& m, double tmax, BvhWalk& w) {
     w.best = -1;
     w.bt = tmax;
 }
-template <class Stack>
+template <bool G1 = false, class Stack>
 RT_DEV int bvh_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const RayInv& inv, BvhWalk& w,
                     const Stack& stk, double shadow_dist) {
     const DevBvhNode& nd = sc.bvh[w.cur];
@@ -1363,7 +1454,7 @@ RT_DEV int bvh_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const 
         for (int k = 0; k < nd.count; ++k) {
             double tt;
             const int id = sc.btri_id[nd.a + k];
-            if (tri_t(sc.btris[nd.a + k], ray, &tt) && (tt < w.bt || (tt == w.bt && (w.best < 0 || id < w.best)))) {
+            if (tri_t<G1>(sc.btris[nd.a + k], ray, &tt) && (tt < w.bt || (tt == w.bt && (w.best < 0 || id < w.best)))) {
                 w.bt = tt;
                 w.best = id;
             }
@@ -1382,6 +1473,7 @@ struct BvhLdsStack {
     LdsI32* p;
     RT_DEV LdsI32& at(int e) const { return p[e * 256]; }
 };
+template <bool G1 = false>
 RT_DEV bool mesh_hit_bvh(const DevScene& sc, const DevMesh& m, const Ray& ray, const RayInv& inv, double tmax,
                          double* t, int* prim) {
     if (m.bvh_n <= 0) return false;
@@ -1389,7 +1481,7 @@ RT_DEV bool mesh_hit_bvh(const DevScene& sc, const DevMesh& m, const Ray& ray, c
     BvhWalk w;
     bvh_begin(m, tmax, w);
     int st;
-    while ((st = bvh_step(sc, m, ray, inv, w, stk, -1.0)) == 0) {
+    while ((st = bvh_step<G1>(sc, m, ray, inv, w, stk, -1.0)) == 0) {
     }
     if (st != 1) return false;
     *t = w.bt;
@@ -1398,21 +1490,22 @@ RT_DEV bool mesh_hit_bvh(const DevScene& sc, const DevMesh& m, const Ray& ray, c
 }
 
 // Whole traversal in one call (megakernel / trace kernel).
-template <bool Slots>
+template <bool Slots, bool G1 = false>
 RT_DEV bool mesh_hit_walk(const DevScene& sc, const DevMesh& m, const Ray& ray, const RayInv& inv, double tmax,
                           double* t, int* prim) {
     OctWalk w;
     if (!walk_begin<Slots>(sc, m, ray, inv, tmax, w)) return false;
     int st;
-    while ((st = walk_step<Slots>(sc, m, ray, inv, w, t, prim)) == WALK_RUN) {
+    while ((st = walk_step<Slots, 256, RT_WALK_HOIST, LdsAncI32, G1>(sc, m, ray, inv, w, t, prim)) == WALK_RUN) {
     }
     return st == WALK_HIT;
 }
 // The slot walk when the scene has its tables (DevScene::node_slot), else the node_kids walk.
+template <bool G1 = false>
 RT_DEV bool mesh_hit(const DevScene& sc, const DevMesh& m, const Ray& ray, const RayInv& inv, double tmax, double* t,
                      int* prim) {
-    if (RT_WALK_TIGHT && sc.node_slot) return mesh_hit_walk<true>(sc, m, ray, inv, tmax, t, prim);
-    return mesh_hit_walk<false>(sc, m, ray, inv, tmax, t, prim);
+    if (RT_WALK_TIGHT && sc.node_slot) return mesh_hit_walk<true, G1>(sc, m, ray, inv, tmax, t, prim);
+    return mesh_hit_walk<false, G1>(sc, m, ray, inv, tmax, t, prim);
 }
 
 // Kernel specialisation by scene features (chosen on the host per scene/flags): code paths a
@@ -1426,8 +1519,10 @@ struct Cfg {
     static constexpr bool bvh = (F & 16) != 0;     // RT_FLAG_MESH_NEAREST: nearest-triangle meshes via the BVH
     static constexpr bool nospec = (F & 32) != 0;  // no specular (mirror) object: the mirror paths compile out
     static constexpr bool ldsobj = (F & 64) != 0;  // the kernel holds the object table in LDS (rt_lds_objects)
+    static constexpr bool g1 = (F & 128) != 0;     // the one-ballot guards (rcp_safe_all's G1): the fused mesh instances
 };
 constexpr int kCfgLdsObj = 64;
+constexpr int kCfgGuards1 = 128;
 
 // The object table of compact scenes in LDS (16 x 208 B): a megakernel instantiated with Cfg bit 64
 // copies DevScene::objects here at its start (lds_objects_fill), so the shading's per-lane object reads
@@ -1474,10 +1569,10 @@ RT_DEV CTab* tables(const DevScene& sc) { return tables_form<false>(sc); }
 template <class C>
 RT_DEV bool object_t(const DevScene& sc, const DevObject& o, const Ray& ray, const RayInv& inv, double* t, int* prim,
                      double tmax = INFINITY) {
-    if (o.geom == GEOM_SPHERE) return sphere_t(o, ray, t);
+    if (o.geom == GEOM_SPHERE) return sphere_t<C::g1>(o, ray, t);
     if (o.geom == GEOM_PLANE) return plane_t(o, ray, inv, t);
-    if constexpr (C::mesh && C::bvh) return mesh_hit_bvh(sc, sc.meshes[o.mesh], ray, inv, tmax, t, prim);
-    if constexpr (C::mesh && !C::bvh) return mesh_hit(sc, sc.meshes[o.mesh], ray, inv, tmax, t, prim);
+    if constexpr (C::mesh && C::bvh) return mesh_hit_bvh<C::g1>(sc, sc.meshes[o.mesh], ray, inv, tmax, t, prim);
+    if constexpr (C::mesh && !C::bvh) return mesh_hit<C::g1>(sc, sc.meshes[o.mesh], ray, inv, tmax, t, prim);
     return false;
 }
 
@@ -1502,14 +1597,14 @@ RT_DEV void consider(HitRec& h, double t, int idx, int prim) {
 // Sphere test on the compact table (same operations as sphere_t; r*r precomputed exactly).
 // (Conservative culls of spheres beyond tmax / below eps before the square root measured 4% slower
 // on cornell_box: the extra compares cost more than the divergent roots they skip.)
-template <class P>
+template <bool G1 = false, class P>
 RT_DEV bool sphere_c(P c, const Ray& ray, double* tout) {
     V3 op = v3(c[0], c[1], c[2]) - ray.o;
     double b = dot(op, ray.d);
     double det = b * b - dot(op, op) + c[3];
     if (det < 0.) return false;
     RT_DBG_REGION(11);
-    det = sqrt_rn(det);
+    det = sqrt_rn<G1>(det);
     double t = b - det;
     if (t > 1e-4) { *tout = t; return true; }
     t = b + det;
@@ -1540,7 +1635,7 @@ RT_DEV HitRec trace_closest(const DevScene& sc, const Ray& ray) {
     CTab* T = tables(sc);
     HitRec h{0.0, -1, -1};
     RT_DBG_TSTART(t_pl);
-    const RayInv inv = make_inv(ray.d);
+    const RayInv inv = make_inv<C::g1>(ray.d);
     if constexpr (C::compact) {
         auto visit = [&](double t, int idx, int prim) { consider(h, t, idx, prim); };
         axis_planes<0>(sc, T, ray, inv, visit);
@@ -1551,7 +1646,7 @@ RT_DEV HitRec trace_closest(const DevScene& sc, const Ray& ray) {
 #pragma unroll
         for (int i = 0; i < kMaxSpheres; ++i) {
             double t;
-            if (i < T->n_sph && sphere_c(T->sph[i], ray, &t)) consider(h, t, T->sph_idx[i], -1);
+            if (i < T->n_sph && sphere_c<C::g1>(T->sph[i], ray, &t)) consider(h, t, T->sph_idx[i], -1);
         }
         RT_DBG_TEND(14, t_sp);
         for (int i = 0; i < T->n_gen; ++i) {
@@ -1580,7 +1675,7 @@ RT_DEV void surface(const DevScene& sc, const Ray& ray, const HitRec& h, V3* pos
     const DevObject& o = object_at<C>(sc, h.obj);
     if (o.geom == GEOM_SPHERE) {
         V3 p = eval(ray, h.t);
-        V3 nn = norm(p - ld3(o.pos));
+        V3 nn = norm<C::g1>(p - ld3(o.pos));
         *pos = p;
         *n = dot(nn, -ray.d) >= 0. ? nn : -nn;
     } else if (o.geom == GEOM_PLANE) {
@@ -1630,9 +1725,9 @@ RT_DEV bool visible_ray(const DevScene& sc, V3 y, const Ray& r, double dist) {
                            planes_clear<2>(T, r.o.z, y.z);
         RayInv inv;
         const bool gen = T->n_gen > 0;  // the generic intersectors use the reciprocals too
-        if (gen) inv = make_inv(r.d);
+        if (gen) inv = make_inv<C::g1>(r.d);
         if (!clear) {
-            if (!gen) inv = make_inv(r.d);
+            if (!gen) inv = make_inv<C::g1>(r.d);
             axis_planes<0>(sc, T, r, inv, visit);
             axis_planes<1>(sc, T, r, inv, visit);
             axis_planes<2>(sc, T, r, inv, visit);
@@ -1640,7 +1735,7 @@ RT_DEV bool visible_ray(const DevScene& sc, V3 y, const Ray& r, double dist) {
 #pragma unroll
         for (int i = 0; i < kMaxSpheres; ++i) {
             double t;
-            if (i < T->n_sph && sphere_c(T->sph[i], r, &t)) occluded |= !(t + ERR_MARGIN >= dist);
+            if (i < T->n_sph && sphere_c<C::g1>(T->sph[i], r, &t)) occluded |= !(t + ERR_MARGIN >= dist);
         }
         if (occluded) return false;
         for (int i = 0; i < T->n_gen; ++i) {
@@ -1651,7 +1746,7 @@ RT_DEV bool visible_ray(const DevScene& sc, V3 y, const Ray& r, double dist) {
         }
         return true;
     }
-    const RayInv inv = make_inv(r.d);
+    const RayInv inv = make_inv<C::g1>(r.d);
     for (int pass = 0; pass < (C::mesh ? 2 : 1); ++pass) {
         for (int i = 0; i < sc.n_objects; ++i) {
             const DevObject& o = object_at<C>(sc, i);
@@ -1667,8 +1762,9 @@ RT_DEV bool visible_ray(const DevScene& sc, V3 y, const Ray& r, double dist) {
 template <class C>
 RT_DEV bool visible(const DevScene& sc, V3 x, V3 y) {
     V3 diff = y - x;
-    double dist = mag(diff);
-    return visible_ray<C>(sc, y, Ray{x, diff / dist}, dist);  // norm(diff), sharing the magnitude
+    double dist;
+    const V3 dir = div_sqrt<C::g1>(diff, dot(diff, diff), &dist);  // norm(diff), sharing the magnitude
+    return visible_ray<C>(sc, y, Ray{x, dir}, dist);
 }
 
 // ---- pieces of trace_ray / mutually_visible for the wavefront's deferred mesh queries ----
@@ -1823,33 +1919,34 @@ RT_DEV V3 brdf_eval(const DevObject& o, V3 n, V3 out, V3 in) {
     // (every object of a scene without Phong or mirror objects is diffuse)
     if ((C::nospec && !C::phong) || o.brdf == BRDF_DIFFUSE) return RT_OPT_KPI ? ld3(o.kpi) : ld3(o.k) * FRAC_1_PI;
     if (!C::phong || o.brdf == BRDF_SPECULAR) {
-        if (equal_within(in, flip_across(out, n), 0.001)) return ld3(o.k) / dot(n, in);
+        if (equal_within(in, flip_across(out, n), 0.001)) return vdiv<C::g1>(ld3(o.k), dot(n, in));
         return v3(0, 0, 0);
     }
     V3 refl = flip_across(in, n);
     double c = fmax(dot(out, refl), 0.);
     return ld3(o.color_d) * o.ph_kd * FRAC_1_PI +
-           ld3(o.color_s) * o.ph_ks * (double)(o.ph_power + 2) / (2. * PI) * powi(c, o.ph_power);
+           vdiv<C::g1>(ld3(o.color_s) * o.ph_ks * (double)(o.ph_power + 2), 2. * PI) * powi(c, o.ph_power);
 }
+template <bool G1 = false>
 RT_DEV void local_coord(V3 n, V3* u, V3* v, V3* w) {
     *w = n;
     V3 base = fabs(w->x) > 0.1 ? v3(0., 1., 0.) : v3(1., 0., 0.);
-    *u = norm(cross(base, *w));
+    *u = norm<G1>(cross(base, *w));
     *v = cross(*w, *u);
 }
 // sample_incoming (scene.rs:56-98); draws: u1 = d[3], u2 = d[4], u3 = d[5].
 template <class C>
 RT_DEV void brdf_sample(const DevObject& o, V3 n, V3 out, Rng& rng, V3* in, double* pdf) {
     if ((C::nospec && !C::phong) || o.brdf == BRDF_DIFFUSE) {
-        double z = sqrt_rn(rng.uniform());
-        double r = sqrt_rn(1.0 - z * z);
+        double z = sqrt_rn<C::g1>(rng.uniform());
+        double r = sqrt_rn<C::g1>(1.0 - z * z);
         double phi = 2.0 * PI * rng.uniform();
         double sphi, cphi;
         sincos_2pi(phi, &sphi, &cphi);
         double x = r * cphi, y = r * sphi;
         V3 u, v, w;
-        local_coord(n, &u, &v, &w);
-        V3 i = norm(u * x + v * y + w * z);
+        local_coord<C::g1>(n, &u, &v, &w);
+        V3 i = norm<C::g1>(u * x + v * y + w * z);
         *in = i;
         *pdf = dot(n, i) * FRAC_1_PI;
         return;
@@ -1891,10 +1988,10 @@ RT_DEV void light_sample(const DevScene& sc, Rng& rng, V3* y, V3* ny, double* pd
         double z = 2. * xi1 - 1.;
         double sp, cp;
         sincos_2pi(2. * PI * xi2, &sp, &cp);
-        const double sz = sqrt_rn(1.0 - z * z);
+        const double sz = sqrt_rn<C::g1>(1.0 - z * z);
         double x = sz * cp;
         double yy = sz * sp;
-        V3 n = norm(v3(x, yy, z));
+        V3 n = norm<C::g1>(v3(x, yy, z));
         *y = ld3(L.pos) + n * L.r;
         *ny = n;
         *pdf = sc.light_pdf;  // 1.0 / (4.0 * PI * L.r * L.r), same bits (host, rt_api.cpp: upload)
@@ -1912,7 +2009,7 @@ RT_DEV void light_sample(const DevScene& sc, Rng& rng, V3* y, V3* ny, double* pd
     const DevTri& t = sc.tris[m.tri_base + lo];
     double b0 = 1. - sqrt(rng.uniform());
     double b1 = (1. - b0) * rng.uniform();
-    V3 ab = norm(ld3(t.ab)), ac = norm(ld3(t.ac));
+    V3 ab = norm<C::g1>(ld3(t.ab)), ac = norm<C::g1>(ld3(t.ac));
     *y = ab * b0 + ac * b1;
     *ny = ld3(t.n);
     *pdf = 1. / m.surface_area;
@@ -1920,20 +2017,21 @@ RT_DEV void light_sample(const DevScene& sc, Rng& rng, V3* y, V3* ny, double* pd
 RT_DEV double light_pdf_area(const DevScene& sc) { return sc.light_pdf; }
 
 // Camera ray of server.rs:339-357 for subpixel (sx, sy) of pixel (x, y_ref).
+template <bool G1 = false>
 RT_DEV Ray camera_ray(const DevScene& sc, V3 cx, V3 cy, double w, double h, int x, int y, int sx, int sy, double u1,
                       double u2) {
     // the tent filter's two square roots, one per branch in the reference, as one sqrt_rn of the selected
     // radicand per axis (sqrt_rn == sqrt bit for bit; the library form only where a wave holds a 0 or tiny one)
     double r1 = 2. * u1;
-    const double q1 = sqrt_rn(r1 < 1. ? r1 : 2. - r1);
+    const double q1 = sqrt_rn<G1>(r1 < 1. ? r1 : 2. - r1);
     double dx = r1 < 1. ? q1 - 1. : 1. - q1;
     double r2 = 2. * u2;
-    const double q2 = sqrt_rn(r2 < 1. ? r2 : 2. - r2);
+    const double q2 = sqrt_rn<G1>(r2 < 1. ? r2 : 2. - r2);
     double dy = r2 < 1. ? q2 - 1. : 1. - q2;
     // w, h are image sizes in [1, 2^32]: the shared-divisor division is exact (qdiv)
     V3 d = cx * (qdiv(((double)sx + 0.5 + dx) / 2. + (double)x, w, rcp_rn(w)) - 0.5) +
            cy * (qdiv(((double)sy + 0.5 + dy) / 2. + (double)y, h, rcp_rn(h)) - 0.5) + ld3(sc.cam_dir);
-    return Ray{ld3(sc.cam_pos), norm(d)};
+    return Ray{ld3(sc.cam_pos), norm<G1>(d)};
 }
 
 RT_DEV uint8_t as_u8(double v) {  // Rust `as u8`: saturating, NaN -> 0

@@ -58,7 +58,9 @@ __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, Render
                                                           uint32_t* next_sub, long nsub, int refill) {
     // Compact scenes (<= kMaxCompactObjects objects): the object table is copied into LDS, so the
     // shading's per-lane object reads (hit object, light) are ds_reads instead of global loads.
-    using C = Cfg<F | ((RT_OPT_LDSOBJ && (F & 8)) ? kCfgLdsObj : 0)>;
+    // the fused mesh instances (F odd) keep the one-ballot guards (path_f64.h kCfgGuards1: they sit at their
+    // register cap, and the new guards raised their spill counts)
+    using C = Cfg<F | ((RT_OPT_LDSOBJ && (F & 8)) ? kCfgLdsObj : 0) | ((F & 1) ? kCfgGuards1 : 0)>;
 #if RT_KARG_VIEW
     const DevScene& sc = karg_scene();  // the arguments read in place (megakernel_common.h)
     const RenderArgs& a = karg_render_args();
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, Render
             if (__any(now) || (refill > 0 && __popcll(__ballot(need)) >= refill)) {
                 if (now || (refill > 0 && need)) {
                     RT_DBG_REGION(3);
-                    const CameraSample nb = camera_sample(sc, a, subpixel_of(a, id), now ? s : s + nbuf + 1);
+                    const CameraSample nb = camera_sample<C::g1>(sc, a, subpixel_of(a, id), now ? s : s + nbuf + 1);
                     if (now) {
                         begin_path(sc, nb, ps);
                         fresh = false;
@@ -493,7 +495,8 @@ hipError_t launch_finalize_f64(const RenderArgs& a, const double* sub_buf, hipSt
 // sqrt_rn's fast range [2^-767, 2^1024) (every exponent, random and extreme mantissas), counts
 // sqrt_rn(x) != sqrt(x) (the library sequence with its input scaling and 0/inf fixup). sqrt_rn takes
 // its fast path only when the whole wave is in range (a wave vote), so bit equality with the library
-// is what makes a lane's result independent of the other lanes of its wave.
+// is what makes a lane's result independent of the other lanes of its wave; bad[3] and bad[4] (below) check
+// the fused normalise and that property itself, in waves where one lane is outside the fast ranges.
 __global__ void k_selftest_arith(long n, uint64_t seed, unsigned long long* bad) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -519,9 +522,83 @@ __global__ void k_selftest_arith(long n, uint64_t seed, unsigned long long* bad)
     const int sx = -767 + (int)((sel2 >> 16) % 1791);  // [-767, 1023]
     const double x = __longlong_as_double((long long)(((uint64_t)(sx + 1023) << 52) | sm));
     if (__double_as_longlong(sqrt_rn(x)) != __double_as_longlong(sqrt(x))) e |= 4;
+    // bad[3]: the fused normalise div_sqrt(v, x) against s = sqrt(x), v / s (library sqrt, IEEE divisions), root
+    // and quotients, inside the fast range: once for a vector with its own squared length (largest component
+    // 2^h, h in [-383, 510], the others up to 2^-3 of it or +-0, so x lies in [2^-766, 2^1024)), once for the x
+    // drawn above (every exponent of [2^-767, 2^1023], extreme mantissas) under a vector within 2^-100 of its root.
+    const uint64_t m4 = g.next(), m5 = g.next(), m6 = g.next(), sel3 = g.next();
+    const auto comp = [](uint64_t mbits, int ex, uint64_t how) {  // +-(1.m) 2^ex; how & 3 == 3: +-0
+        const uint64_t sign = mbits & 0x8000000000000000ull;
+        if ((how & 3) == 3) return __longlong_as_double((long long)sign);
+        uint64_t mt = mbits & 0xFFFFFFFFFFFFFull;
+        if ((how & 12) == 4) mt = 0;
+        if ((how & 12) == 8) mt = 0xFFFFFFFFFFFFFull;
+        return __longlong_as_double((long long)(sign | ((uint64_t)(ex + 1023) << 52) | mt));
+    };
+    const auto same = [](double p, double q) {  // equal bits, or both NaN
+        return __double_as_longlong(p) == __double_as_longlong(q) || (p != p && q != q);
+    };
+    const auto same_ds = [&](V3 v, double r) {  // div_sqrt(v, r) against the library forms
+        double root;
+        const V3 f = div_sqrt(v, r, &root);
+        const double s = sqrt(r);
+        return same(root, s) && same(f.x, v.x / s) && same(f.y, v.y / s) && same(f.z, v.z / s);
+    };
+    const int h0 = -383 + (int)((sel3 >> 16) % 894);  // [-383, 510]
+    const V3 va = v3(comp(m4, h0, 0), comp(m5, h0 - (int)((sel3 >> 4) & 3), sel3 >> 6),
+                     comp(m6, h0 - (int)((sel3 >> 10) & 3), sel3 >> 12));
+    const double xa = va.x * va.x + va.y * va.y + va.z * va.z;
+    const int hs = sx >> 1;  // the root's exponent (floor)
+    const V3 vb = v3(comp(m4, hs - (int)((sel3 >> 32) % 101), sel3 >> 40), comp(m5, hs - (int)((sel3 >> 44) % 101), 0),
+                     comp(m6, hs, sel3 >> 52));
+    if (!same_ds(va, xa) || !same_ds(vb, x)) e |= 8;
+    // bad[4]: the same comparison plus sqrt_rn, rcp_any and V3 / s where a wave is mixed: in every fourth
+    // wave one lane (its index rotating) holds an operand outside the fast ranges (0, a subnormal, -0, inf, NaN;
+    // 2^-800 or a negative number as radicand; 2^-1000 or 2^1000 as divisor), or one at an edge of the guards'
+    // windows: 2^900 (in rcp_safe, outside the high-dword window), the next double above it, the largest double
+    // below 2^-900, the largest double below 2^-767 as radicand; inside: 2^-767 and the next double, -2^-900, the
+    // largest finite double. Every lane of such a wave must still give the library's bits: that is what makes a
+    // lane's result independent of its wave-mates. Both guard forms are checked (G1: the fused mesh instances').
+    const long wv = i >> 6;
+    double xp = x, bp = b;
+    if ((wv & 3) == 3 && (int)(i & 63) == (int)((wv >> 2) & 63)) {
+        const uint64_t sub = (m4 & 0xFFFFFFFFFFFFFull) | 1ull;  // a subnormal
+        switch ((int)((wv >> 2) % 15)) {
+        case 0: xp = 0.0; bp = 0.0; break;
+        case 1: xp = __longlong_as_double((long long)sub); bp = xp; break;
+        case 2: xp = 0x1p-800; bp = -0.0; break;
+        case 3: xp = INFINITY; bp = INFINITY; break;
+        case 4: xp = __longlong_as_double(0x7FF8000000000000ll); bp = xp; break;
+        case 5: xp = -x; bp = -INFINITY; break;
+        case 6: xp = -0.0; bp = -__longlong_as_double((long long)sub); break;
+        case 7: bp = 0x1p-1000; break;
+        case 8: bp = -0x1p1000; break;
+        case 9: bp = 0x1p900; xp = 0x1p-767; break;
+        case 10: bp = 0x1.0000000000001p900; xp = 0x1.fffffffffffffp-768; break;
+        case 11: bp = -0x1.fffffffffffffp-901; xp = 0x1.fffffffffffffp1023; break;
+        case 12: bp = -0x1p-900; xp = 0x1.0000000000001p-767; break;
+        case 13: bp = 0x1.fffffffffffffp1023; xp = -0x1.fffffffffffffp-768; break;
+        default: bp = 0x1.fffffffffffffp899; xp = 0x1p-768; break;
+        }
+    }
+    bool ok = same_ds(vb, xp) && same(sqrt_rn(xp), sqrt(xp)) && same(rcp_any(bp), 1.0 / bp);
+    ok = ok && same(sqrt_rn<true>(xp), sqrt(xp)) && same(rcp_any<true>(bp), 1.0 / bp);
+    // numerators within 2^+-100 like a (the quotient neither overflows nor underflows), one of them +-0 at times
+    const V3 nv = v3(a, comp(m5, (int)((sel3 >> 20) % 200) - 100, 0), comp(m6, (int)((sel3 >> 28) % 200) - 100, sel3 >> 12));
+    const V3 qv = nv / bp;
+    ok = ok && same(qv.x, nv.x / bp) && same(qv.y, nv.y / bp) && same(qv.z, nv.z / bp);
+    double r1;
+    // (G1 divides by an in-range root of an out-of-range radicand through qdiv: nv keeps that quotient in range too)
+    const V3 q1 = vdiv<true>(nv, bp), d1 = div_sqrt<true>(nv, xp, &r1);
+    const double s1 = sqrt(xp);
+    ok = ok && same(q1.x, nv.x / bp) && same(q1.y, nv.y / bp) && same(q1.z, nv.z / bp);
+    ok = ok && same(r1, s1) && same(d1.x, nv.x / s1) && same(d1.y, nv.y / s1) && same(d1.z, nv.z / s1);
+    if (!ok) e |= 16;
     if (e & 1) atomicAdd(&bad[0], 1ull);
     if (e & 2) atomicAdd(&bad[1], 1ull);
     if (e & 4) atomicAdd(&bad[2], 1ull);
+    if (e & 8) atomicAdd(&bad[3], 1ull);
+    if (e & 16) atomicAdd(&bad[4], 1ull);
 }
 
 // Diagnostic builds: the wave records of the last k_megakernel_f64 launches (start, half-idle, end per wave, on
@@ -549,19 +626,21 @@ extern "C" int rt_debug_last_split(long long out[3]) {
     return 0;
 }
 
-// n_out: the caller's output count (at most 3 are written: reciprocal, quotient, square root)
+// n_out: the caller's output count (at most 5 are written: reciprocal, quotient, square root, fused normalise,
+// mixed waves)
 extern "C" int rt_selftest_arith_n(long n, unsigned long long seed, unsigned long long* out, int n_out) {
+    constexpr int kCounts = 5;
     unsigned long long* d = nullptr;
-    if (n <= 0 || !out || n_out <= 0 || hipMalloc(&d, 3 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (n <= 0 || !out || n_out <= 0 || hipMalloc(&d, kCounts * sizeof(unsigned long long)) != hipSuccess) return -1;
     int rc = 0;
-    unsigned long long h[3] = {0, 0, 0};
-    if (hipMemset(d, 0, 3 * sizeof(unsigned long long)) != hipSuccess) rc = -1;
+    unsigned long long h[kCounts] = {0, 0, 0, 0, 0};
+    if (hipMemset(d, 0, kCounts * sizeof(unsigned long long)) != hipSuccess) rc = -1;
     if (!rc) {
         hipLaunchKernelGGL(k_selftest_arith, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, seed, d);
         if (hipGetLastError() != hipSuccess || hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
     }
     (void)hipFree(d);
-    for (int i = 0; i < n_out && i < 3; ++i) out[i] = h[i];
+    for (int i = 0; i < n_out && i < kCounts; ++i) out[i] = h[i];
     return rc;
 }
 // The original two-output entry point (reciprocal, quotient), kept for callers built against it.
