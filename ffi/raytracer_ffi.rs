@@ -185,6 +185,25 @@ extern "C" {
         t: *mut f64, object: *mut i32, pos: *mut f64, normal: *mut f64,
     ) -> c_int;
 
+    /// First-hit feature buffers of the tile: `feat_out` tile_w * tile_h * 8 floats (mean normal, mean hit
+    /// distance, mean albedo, coverage; rt_ffi.h).
+    pub fn rt_render_features(scene: *const RtScene, params: *const RtRenderParams, feat_out: *mut f32) -> c_int;
+    /// The same into a device buffer, enqueued on `stream`.
+    pub fn rt_render_features_device(
+        scene: *const RtScene, params: *const RtRenderParams, d_feat: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
+    /// Edge-avoiding a-trous filter over `rt_render`'s `sub_out` (whole image) guided by the features;
+    /// `levels` 0..8 (0: pass-through), a sigma <= 0 drops its term; `lin_out` nullable.
+    pub fn rt_denoise(
+        device: i32, width: i32, height: i32, sub: *const f64, feat: *const f32, levels: i32, sigma_c: f32,
+        sigma_n: f32, sigma_z: f32, sigma_a: f32, rgb_out: *mut u8, lin_out: *mut f32,
+    ) -> c_int;
+    /// The same on device buffers; waits for the filter and frees its scratch before returning.
+    pub fn rt_denoise_device(
+        device: i32, width: i32, height: i32, sub: *const f64, feat: *const f32, levels: i32, sigma_c: f32,
+        sigma_n: f32, sigma_z: f32, sigma_a: f32, rgb_out: *mut u8, lin_out: *mut f32, stream: *mut c_void,
+    ) -> c_int;
+
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_abi_version() -> c_int;
     pub fn rt_device_count() -> c_int;

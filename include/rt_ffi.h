@@ -13,6 +13,7 @@
  *   rt_render_multi     <- same, bands handed out dynamically to several devices (the row-band fan-out of
  *                          RenderJob::run, server.rs:165-168), host gather
  *   rt_trace_rays       <- Scene::trace_ray                  src/scene.rs:272-289 (batch form, for parity tests)
+ *   rt_render_features, rt_denoise: no counterpart in the reference (denoised previews at low spp)
  *
  * Conventions (mirroring the reference's):
  *   - a scene is immutable after creation and may be shared by concurrent rt_render calls
@@ -37,7 +38,9 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 3  /* 2: rt_render_params.row_step; 3: rt_render_multi */
+#define RT_ABI_VERSION 3  /* 2: rt_render_params.row_step; 3: rt_render_multi. The denoised-preview entry points
+                             (rt_render_features*, rt_denoise*) are additive: no struct or existing call changed, so
+                             the version stays 3 */
 
 /* return codes */
 #define RT_OK 0
@@ -171,6 +174,39 @@ int rt_trace_rays(const rt_scene* scene, int32_t device, int64_t n, const double
 /* The same with render flags (RT_FLAG_MESH_NEAREST selects the nearest-triangle mesh semantics). */
 int rt_trace_rays_flags(const rt_scene* scene, int32_t device, uint32_t flags, int64_t n, const double* origins,
                         const double* dirs, double* t, int32_t* object, double* pos, double* normal);
+
+/* Denoised previews -------------------------------------------------------------- */
+/* First-hit feature buffers of the tile of `params` (width, height, x0, y0, tile_w, tile_h, row_step, device and
+ * RT_FLAG_MESH_NEAREST are used; spp, seed and the other flags are ignored). Per subpixel, the camera ray through the
+ * tent filter's centre (the ray sample_pixel would trace with dx = dy = 0) is traced like rt_trace_rays; the pixel's
+ * four results are summed as (s0 + s1) + (s2 + s3) in f64. feat_out: tile_w * tile_h * 8 floats, per pixel
+ *   [0..2] mean hit normal (as rt_trace_rays reports it, not renormalised)   [3] mean hit distance t
+ *   [4..6] mean albedo: clamp(base + emitted, 0, 1) per channel, base = k (diffuse, specular) or
+ *          phong_kd * color_d + phong_ks * color_s (Phong)                   [7] coverage = hits / 4
+ * each mean over the rays that hit, 0 when none did. */
+int rt_render_features(const rt_scene* scene, const rt_render_params* params, float* feat_out);
+/* The same into a device buffer on params->device, enqueued on `stream` (hipStream_t, NULL = default stream);
+ * returns without waiting for the device. */
+int rt_render_features_device(const rt_scene* scene, const rt_render_params* params, void* d_feat, void* stream);
+/* Edge-avoiding a-trous wavelet filter. sub: width * height * 12 f64, rt_render's sub_out of the whole image being
+ * filtered; feat: width * height * 8 floats as above. c0 = sum_j clamp(sub_j, 0, 1) * 0.25 (f64, rounded to f32); for
+ * level i = 0 .. levels - 1, step s = 2^i, taps q = p + s (dx, dy), dx, dy in -2..2, inside the image, in row-major
+ * (dy, dx) order, h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *   E = |c_p - c_q|^2 / (sigma_c 2^-i)^2 + |n_p - n_q|^2 / sigma_n^2
+ *     + ((z_p - z_q) / (z_p + z_q + 1e-20))^2 / sigma_z^2 + (|a_p - a_q|^2 + (k_p - k_q)^2) / sigma_a^2
+ *   c'_p = sum_q w c_q / sum_q w,   w = h[dx + 2] h[dy + 2] exp(-E)
+ * (n, z, a, k: feat[0..2], [3], [4..6], [7]; f32 arithmetic). A sigma <= 0 drops its term. levels is 0..8; 0 is the
+ * pass-through: rgb_out is then rt_render's rgb_out byte for byte. rgb_out: width * height * 3 u8 through rt_render's
+ * gamma and `as u8`; lin_out (optional): width * height * 3 floats, the filtered linear colour. No hidden defaults:
+ * every parameter is the caller's. */
+int rt_denoise(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat, int32_t levels,
+               float sigma_c, float sigma_n, float sigma_z, float sigma_a, uint8_t* rgb_out, float* lin_out);
+/* The same on device buffers of `device` (sub and feat 16-byte aligned), enqueued on `stream`; the call waits for the
+ * filter. Its scratch (32 bytes per pixel) is freed before it returns, except that one idle buffer of at most 128 MiB is
+ * kept for the next call. */
+int rt_denoise_device(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
+                      int32_t levels, float sigma_c, float sigma_n, float sigma_z, float sigma_a, uint8_t* rgb_out,
+                      float* lin_out, void* stream);
 
 const char* rt_last_error(void);
 int rt_abi_version(void);

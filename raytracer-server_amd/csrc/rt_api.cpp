@@ -17,6 +17,7 @@
 #include "ab_knobs.h"
 #include "device/scene_layout.h"
 #include "host/scene_host.hpp"
+#include "kernels/denoise.h"
 #include "kernels/kernels.h"
 #include "kernels/wavefront.h"
 
@@ -1452,6 +1453,214 @@ int rt_trace_rays_flags(const rt_scene* scene, int32_t device, uint32_t flags, i
     (void)hipFree(buf);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_trace_rays: ") + hipGetErrorString(e));
     return RT_OK;
+}
+
+// Denoised previews ---------------------------------------------------------------------
+
+namespace {
+
+// The ordinal names a visible HIP device: RT_E_NODEVICE without one (or without the runtime), as rt_render_multi.
+int need_device(const char* who, int32_t device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
+        (void)hipGetLastError();
+        return fail(RT_E_NODEVICE, std::string(who) + ": no HIP device visible");
+    }
+    if (device < 0 || device >= n)
+        return fail(RT_E_INVAL, std::string(who) + ": device ordinal " + std::to_string(device) + " out of range");
+    return RT_OK;
+}
+
+int check_features(const char* who, const rt_scene* scene, const rt_render_params* p, const void* out) {
+    if (!scene || !p || !out) return fail(RT_E_INVAL, std::string(who) + ": null argument");
+    return check_params(p);
+}
+
+int check_denoise(const char* who, int32_t width, int32_t height, const void* sub, const void* feat, int32_t levels,
+                  const float sigma[4], const void* rgb_out) {
+    if (!sub || !feat || !rgb_out) return fail(RT_E_INVAL, std::string(who) + ": null argument");
+    if (width < 1 || height < 1) return fail(RT_E_INVAL, std::string(who) + ": width/height must be positive");
+    if ((int64_t)width * height > (int64_t)INT32_MAX) return fail(RT_E_INVAL, std::string(who) + ": image too large");
+    if (levels < 0 || levels > 8) return fail(RT_E_INVAL, std::string(who) + ": levels must be in 0..8");
+    for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(sigma[i])) return fail(RT_E_INVAL, std::string(who) + ": sigma must be finite");
+    return RT_OK;
+}
+
+int features_enqueue(rt_scene* s, const rt_render_params* p, float* d_feat, hipStream_t st) {
+    HIP_TRY(hipSetDevice(p->device));
+    rt::DevScene ds;
+    const int rc = upload(s, p->device, &ds);
+    if (rc != RT_OK) return rc;
+    rt::FeatArgs a{};
+    a.width = p->width;
+    a.height = p->height;
+    a.x0 = p->x0;
+    a.y0 = p->y0;
+    a.tw = p->tile_w;
+    a.th = p->tile_h;
+    a.row_step = p->row_step > 1 ? p->row_step : 1;
+    a.nearest = (p->flags & RT_FLAG_MESH_NEAREST) && !s->host.meshes.empty();
+    rt::host::camera_frame(s->host, p->width, p->height, a.cx, a.cy);
+    HIP_TRY(rt::launch_features_f64(ds, a, d_feat, st));
+    return RT_OK;
+}
+
+// The filter's scratch (32 bytes per pixel): one idle buffer of at most kScratchKeep bytes is kept for the next
+// call (a 1080p frame needs 66 MB; a preview server filters frame after frame), anything else is freed when the call
+// returns. A call that finds the kept buffer taken, too small or on another device allocates its own.
+constexpr size_t kScratchKeep = (size_t)128 << 20;
+struct ScratchKeep {
+    std::mutex mu;
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    int device = -1;
+} g_scratch;
+
+void* scratch_take(int device, size_t bytes, hipError_t* err) {
+    {
+        std::lock_guard<std::mutex> lk(g_scratch.mu);
+        if (g_scratch.ptr && g_scratch.device == device && g_scratch.bytes >= bytes) {
+            void* p = g_scratch.ptr;
+            g_scratch.ptr = nullptr;
+            return p;
+        }
+    }
+    void* p = nullptr;
+    *err = hipMalloc(&p, bytes);
+    return *err == hipSuccess ? p : nullptr;
+}
+// (the stream that used it has been waited for)
+void scratch_give(int device, void* p, size_t bytes) {
+    void* drop = p;
+    if (bytes <= kScratchKeep) {
+        std::lock_guard<std::mutex> lk(g_scratch.mu);
+        if (!g_scratch.ptr || g_scratch.bytes < bytes) {  // keep the larger one
+            drop = g_scratch.ptr;
+            const int drop_dev = g_scratch.device;
+            g_scratch.ptr = p;
+            g_scratch.bytes = bytes;
+            g_scratch.device = device;
+            if (drop && drop_dev != device) {
+                (void)hipSetDevice(drop_dev);
+                (void)hipFree(drop);
+                (void)hipSetDevice(device);
+                drop = nullptr;
+            }
+        }
+    }
+    if (drop) (void)hipFree(drop);
+}
+
+// Enqueues the filter on `st` and waits for it, so its scratch is idle again when the call returns.
+int denoise_run(int32_t device, int32_t width, int32_t height, const double* d_sub, const float* d_feat,
+                int32_t levels, const float sigma[4], uint8_t* d_rgb, float* d_lin, hipStream_t st) {
+    const long npix = (long)width * height;
+    hipError_t e = hipSuccess;
+    if (levels == 0) {
+        // the pass-through: rt_render's own RGB8 (k_finalize_f64), byte for byte
+        rt::RenderArgs a{};
+        a.tw = width;
+        a.th = height;
+        a.rgb_out = d_rgb;
+        e = rt::launch_finalize_f64(a, d_sub, st);
+        if (e == hipSuccess && !d_lin) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(RT_E_HIP, std::string("denoise: ") + hipGetErrorString(e));
+        if (!d_lin) return RT_OK;
+    }
+    const size_t bytes = rt::atrous_scratch_bytes(npix);
+    void* scratch = scratch_take(device, bytes, &e);
+    if (!scratch)
+        return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, std::string("denoise scratch: ") + hipGetErrorString(e));
+    e = rt::launch_atrous(width, height, d_sub, d_feat, levels, sigma[0], sigma[1], sigma[2], sigma[3], scratch,
+                          levels == 0 ? nullptr : d_rgb, d_lin, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    scratch_give(device, scratch, bytes);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("denoise: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+}  // namespace
+
+int rt_render_features_device(const rt_scene* scene, const rt_render_params* params, void* d_feat, void* stream) {
+    int rc = check_features("rt_render_features_device", scene, params, d_feat);
+    if (rc == RT_OK) rc = need_device("rt_render_features_device", params->device);
+    if (rc != RT_OK) return rc;
+    return features_enqueue(const_cast<rt_scene*>(scene), params, (float*)d_feat, (hipStream_t)stream);
+}
+
+int rt_render_features(const rt_scene* scene, const rt_render_params* p, float* feat_out) {
+    int rc = check_features("rt_render_features", scene, p, feat_out);
+    if (rc == RT_OK) rc = need_device("rt_render_features", p->device);
+    if (rc != RT_OK) return rc;
+    const size_t bytes = (size_t)p->tile_w * p->tile_h * rt::kFeatFloats * sizeof(float);
+    if (bytes == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    float* d_feat = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_feat, bytes));
+    rc = features_enqueue(const_cast<rt_scene*>(scene), p, d_feat, nullptr);
+    std::string err = g_err;
+    if (rc == RT_OK) {
+        hipError_t e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess) e = hipMemcpy(feat_out, d_feat, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_render_features: ") + hipGetErrorString(e); }
+    } else {
+        (void)hipStreamSynchronize(nullptr);
+    }
+    (void)hipFree(d_feat);
+    return rc < 0 ? fail(rc, err) : rc;
+}
+
+int rt_denoise_device(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
+                      int32_t levels, float sigma_c, float sigma_n, float sigma_z, float sigma_a, uint8_t* rgb_out,
+                      float* lin_out, void* stream) {
+    const float sigma[4] = {sigma_c, sigma_n, sigma_z, sigma_a};
+    int rc = check_denoise("rt_denoise_device", width, height, sub, feat, levels, sigma, rgb_out);
+    if (rc == RT_OK) rc = need_device("rt_denoise_device", device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    return denoise_run(device, width, height, sub, feat, levels, sigma, rgb_out, lin_out, (hipStream_t)stream);
+}
+
+int rt_denoise(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat, int32_t levels,
+               float sigma_c, float sigma_n, float sigma_z, float sigma_a, uint8_t* rgb_out, float* lin_out) {
+    const float sigma[4] = {sigma_c, sigma_n, sigma_z, sigma_a};
+    int rc = check_denoise("rt_denoise", width, height, sub, feat, levels, sigma, rgb_out);
+    if (rc == RT_OK) rc = need_device("rt_denoise", device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t npix = (size_t)width * height;
+    const size_t b_sub = npix * 12 * sizeof(double), b_feat = npix * rt::kFeatFloats * sizeof(float);
+    const size_t b_lin = npix * 3 * sizeof(float), b_rgb = align_up(npix * 3, 16);
+    // one allocation: sub | feat | lin | rgb (each part 16-byte aligned)
+    char* buf = nullptr;
+    hipError_t e = hipMalloc((void**)&buf, b_sub + b_feat + b_lin + b_rgb + 16);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, std::string("rt_denoise buffers: ") + hipGetErrorString(e));
+    double* d_sub = (double*)buf;
+    float* d_feat = (float*)(buf + b_sub);
+    float* d_lin = (float*)(buf + b_sub + b_feat);
+    uint8_t* d_rgb = (uint8_t*)(buf + align_up(b_sub + b_feat + b_lin, 16));
+    hipStream_t st = nullptr;
+    e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_sub, sub, b_sub, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_feat, feat, b_feat, hipMemcpyHostToDevice, st);
+    std::string err;
+    if (e == hipSuccess) {
+        rc = denoise_run(device, width, height, d_sub, d_feat, levels, sigma, d_rgb, lin_out ? d_lin : nullptr, st);
+        err = g_err;
+    }
+    if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync(rgb_out, d_rgb, npix * 3, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && rc == RT_OK && lin_out) e = hipMemcpyAsync(lin_out, d_lin, b_lin, hipMemcpyDeviceToHost, st);
+    if (st) {
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = es;
+        (void)hipStreamDestroy(st);
+    }
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_denoise: ") + hipGetErrorString(e));
+    return rc < 0 ? fail(rc, err) : rc;
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@ streaming, band by band, top to bottom), the cancel flag is also polled inside t
 reference's panics (bad JSON, unknown scene) become logged errors.
 
 Run:  PORT=8080 python -m rt_amd.server <scenes dir>
+      RT_DENOISE=<levels> selects denoised previews (whole frames through rt_amd.render_denoised).
 """
 import asyncio
 import ctypes
@@ -48,6 +49,20 @@ def gpu_band_renderer(device=0, fp32=False):
         rgb, _, st = rt_amd.render(scene, width, height, spp, seed, tile=(0, y0, width, rows),
                                    megakernel=True, device=device, cancel=cancel, fp32=fp32)
         return None if st["cancelled"] else rgb
+
+    return render
+
+
+def gpu_denoised_frame_renderer(device=0, **denoise_params):
+    """Whole-frame renderer with a denoised preview (rt_amd.render_denoised: render + feature buffers + the a-trous
+    filter), for a server run with band_rows = height: the filter at a row reads rows up to
+    2 * (2^levels - 1) away, so it renders, filters the whole frame and returns the rows it is asked for.
+    denoise_params: levels / sigma_* (rt_amd.DENOISE_DEFAULTS otherwise)."""
+    import rt_amd
+
+    def render(scene, width, height, spp, seed, y0, rows, cancel):
+        rgb = rt_amd.render_denoised(scene, width, height, spp, seed, device=device, cancel=cancel, **denoise_params)
+        return None if rgb is None else rgb[y0:y0 + rows]
 
     return render
 
@@ -178,7 +193,14 @@ def main(argv=None):
         # (geometry.rs:886-903), not the reference's first-hit octree walk (geometry.rs:1237-1295)
         print("RT_PRECISION=f32: f32 perf mode; meshes (flying_unicorn) use nearest-triangle hits, not the "
               "reference's octree semantics; frames differ statistically from server.rs", file=sys.stderr)
-    web.run_app(Server(scenes, renderer=gpu_band_renderer(fp32=fp32)).app(), host="0.0.0.0", port=port, print=None)
+    if "RT_DENOISE" in os.environ:
+        # denoised previews: whole frames (the filter needs an apron of 2 * (2^levels - 1) rows around a band)
+        levels = int(os.environ["RT_DENOISE"])
+        print(f"RT_DENOISE={levels}: whole-frame renders, {levels}-level a-trous filter", file=sys.stderr)
+        server = Server(scenes, renderer=gpu_denoised_frame_renderer(levels=levels), band_rows=HEIGHT)
+    else:
+        server = Server(scenes, renderer=gpu_band_renderer(fp32=fp32))
+    web.run_app(server.app(), host="0.0.0.0", port=port, print=None)
     return 0
 
 
