@@ -4,6 +4,7 @@
  */
 #ifndef RT_DIAG_H
 #define RT_DIAG_H
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -54,6 +55,46 @@ int rt_debug_last_split(long long out[3]);
  * cleared. For
  * n_waves <= 8192. Returns 0, 1 without the timers (zeros), -1 on a HIP error. */
 int rt_debug_wave_times(unsigned long long* out, int n_waves);
+
+/* Batch queries through the query code of one kernel family, one lane per query (tests/test_gpu_queries.py
+ * compares every form with the CPU oracle ray by ray). `form` names whose code answers the queries:
+ *   RT_DIAG_FUSED        trace_closest<C> / visible<C> (x, y -> div_sqrt -> visible_ray) with C as k_trace_f64
+ *                        chooses it: the fused mesh instances of k_megakernel_f64; with RT_FLAG_MESH_NEAREST the
+ *                        BVH walks of the nearest-triangle mode.
+ *   RT_DIAG_FUSED_G0     the same through the even-F instance that k_megakernel_f64<8, 4> runs for a mesh-free
+ *                        compact scene (the round-7 range guards); RT_E_INVAL for a scene with meshes.
+ *   RT_DIAG_SPLIT_SLOTS  trace_analytic / visible_analytic, mesh_near_mask (the f32 cull) at the analytic t (or
+ *                        infinity) resp. |y - x|, then the slot walk (walk_step<true>) of each near mesh in gen
+ *                        order, begun as the pools begin it, merged by consider resp. occluded iff a walk's hit has
+ *                        !(t + 0.001 >= |y - x|): k_megakernel_roles_f64 and k_megakernel_mesh_f64's walk pool.
+ *   RT_DIAG_SPLIT_KIDS   the same split with the node_kids walk (walk_step<false>) begun with its own f64 cull for
+ *                        every mesh of a candidate ray: the wavefront's k_wf_mesh_closest / k_wf_shadow_mesh.
+ *   RT_DIAG_SPLIT_FLAT   the same split with flat_query per near mesh: k_megakernel_fpool_f64; RT_E_INVAL unless
+ *                        every mesh of the scene is a flat octree (and there are at most two).
+ *   RT_DIAG_FUSED_G1     the fused form through the instances k_megakernel_f64<odd, 3> runs for a compact scene with
+ *                        meshes: the one-ballot range guards those keep (path_f64.h kCfgGuards1), which k_trace_f64's
+ *                        choice of C does not carry; octree walks, or the BVH with RT_FLAG_MESH_NEAREST.
+ * The split forms and FUSED_G1 need a compact scene with meshes; only FUSED and FUSED_G1 take a flag (RT_E_INVAL
+ * otherwise); flags: 0 or RT_FLAG_MESH_NEAREST (rt_ffi.h). Host arrays. A null pointer (near_mask may be null),
+ * n < 0, an unknown form or flag: RT_E_INVAL; then n == 0: RT_OK; then no visible HIP device: RT_E_NODEVICE. */
+#define RT_DIAG_FUSED 0
+#define RT_DIAG_FUSED_G0 1
+#define RT_DIAG_SPLIT_SLOTS 2
+#define RT_DIAG_SPLIT_KIDS 3
+#define RT_DIAG_SPLIT_FLAT 4
+#define RT_DIAG_FUSED_G1 5
+struct rt_scene;
+/* Scene::trace_ray for n rays (o, d: [n][3]): t[n] (0 for a miss), obj[n] (-1 for a miss), prim[n] (the hit
+ * triangle's scene-wide index, -1 unless a mesh was hit), pos / nrm [n][3] through surface<> as k_trace_f64
+ * (zeros for a miss). The split forms' near mask comes out of rt_diag_visible only: a mesh culled wrongly here
+ * shows as a different hit object. */
+int rt_diag_trace(const struct rt_scene* scene, int32_t device, int32_t form, uint32_t flags, int64_t n, const double* o,
+                  const double* d, double* t, int32_t* obj, int32_t* prim, double* pos, double* nrm);
+/* Scene::mutually_visible for n segments (x, y: [n][3]): vis[n] = 1 visible, 0 occluded; near_mask[n] (may be
+ * null): the mask of meshes the split form's cull let through (bit m: mesh m; computed whether or not an
+ * analytic object already blocks the segment), 0 for the fused forms. */
+int rt_diag_visible(const struct rt_scene* scene, int32_t device, int32_t form, uint32_t flags, int64_t n, const double* x,
+                    const double* y, uint8_t* vis, uint32_t* near_mask);
 #ifdef __cplusplus
 }
 #endif

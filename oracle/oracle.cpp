@@ -969,6 +969,12 @@ void orc_trace(orc_scene_t* sc, int64_t n, const double* o, const double* d, dou
     }
 }
 
+// Scene::mutually_visible (scene.rs:258-270) for a batch of segments x -> y: out = 1 visible, 0 occluded.
+void orc_visible(orc_scene_t* sc, int64_t n, const double* x, const double* y, uint8_t* out) {
+    for (int64_t i = 0; i < n; ++i)
+        out[i] = mutually_visible(sc->s, v3(x[3*i], x[3*i+1], x[3*i+2]), v3(y[3*i], y[3*i+1], y[3*i+2])) ? 1 : 0;
+}
+
 // RenderJob::run (server.rs:157-199) over a tile of screen rows [y0, y0+th) x [x0, x0+tw):
 // the pixel at screen row `row` is sample_pixel(x, height-row-1, ...). Pixel id for the RNG is
 // row*width + x (global, so output is independent of tiling). rgb: th*tw*3 (row-major, top row

@@ -80,4 +80,33 @@ hipError_t launch_finalize_f64(const RenderArgs& a, const double* sub_buf, hipSt
 hipError_t launch_trace_f64(const DevScene& sc, long n, const double* o, const double* d, double* t, int32_t* obj,
                             double* pos, double* nrm, bool mesh_nearest, hipStream_t st);
 
+// Batch query diagnostics (include/rt_diag.h rt_diag_trace / rt_diag_visible, kernels/diag_queries.h): n queries,
+// one lane each. a / b: the rays' origins and directions (trace: t, obj, prim, pos, nrm out) or the segments'
+// endpoints x and y (visible: vis out); near_mask (device, may be null): the split forms' mesh_near_mask.
+struct DiagArgs {
+    long n;
+    const double* a;
+    const double* b;
+    double* t;
+    int32_t* obj;
+    int32_t* prim;
+    double* pos;
+    double* nrm;
+    uint8_t* vis;
+    uint32_t* near_mask;
+};
+// Each launcher sits in the translation unit that owns the query code it runs; visible: the segment query
+// instead of the ray query.
+// render_f64.hip: trace_closest<C> / visible<C> with k_trace_f64's Cfg choice (guards 0), the mesh-free compact
+// instance of k_megakernel_f64<8, 4> (1: the round-7 guards), or the compact mesh instances of
+// k_megakernel_f64<odd, 3> (2: the one-ballot guards, kCfgGuards1)
+hipError_t launch_diag_fused(const DevScene& sc, const DiagArgs& a, bool visible, int guards, bool mesh_nearest,
+                             hipStream_t st);
+// render_mesh_f64.hip: the roles / walk pools' split (analytic part, mesh_near_mask, slot walks of the near meshes)
+hipError_t launch_diag_slots(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st);
+// wavefront_f64.hip: the wavefront's split (analytic part, mesh_candidate, node_kids walks)
+hipError_t launch_diag_kids(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st);
+// render_flat_f64.hip: the flat query pool's split (analytic part, near mask, flat_query per near mesh)
+hipError_t launch_diag_flat(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st);
+
 }  // namespace rt

@@ -11,6 +11,7 @@
 #include "../device/integrator_f64.h"
 #include "kernels.h"
 #include "megakernel_common.h"
+#include "diag_queries.h"
 
 namespace rt {
 using namespace f64;
@@ -371,6 +372,44 @@ __global__ __launch_bounds__(256) void k_trace_f64(DevScene sc, long n, const do
         pos[3 * i] = p.x; pos[3 * i + 1] = p.y; pos[3 * i + 2] = p.z;
         nrm[3 * i] = nn.x; nrm[3 * i + 1] = nn.y; nrm[3 * i + 2] = nn.z;
     }
+}
+
+// rt_diag_trace / rt_diag_visible, the fused forms: trace_closest<C> / visible<C> per lane, C as k_trace_f64
+// chooses it (cfg 0..3: compact | nearest << 1), cfg 4: the mesh-free compact instance the analytic
+// megakernel k_megakernel_f64<8, 4> runs (even F: the round-7 guards, no mesh code compiled in), or cfg 5 / 6:
+// the compact mesh instances with the one-ballot guards (kCfgGuards1) that k_megakernel_f64<odd, 3> keeps.
+template <class C>
+RT_DEV void diag_fused_query(const DevScene& sc, const DiagArgs& a, long i, int vis) {
+    if (vis) {
+        const V3 x = v3(a.a[3 * i], a.a[3 * i + 1], a.a[3 * i + 2]), y = v3(a.b[3 * i], a.b[3 * i + 1], a.b[3 * i + 2]);
+        diag_store_vis(a, i, visible<C>(sc, x, y), 0u);
+    } else {
+        const Ray r = diag_ray(a, i);
+        diag_store_hit(sc, a, i, r, trace_closest<C>(sc, r), 0u);
+    }
+}
+template <int F>
+__global__ __launch_bounds__(256) void k_diag_fused(DevScene sc, DiagArgs a, int vis) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    diag_fused_query<Cfg<F>>(sc, a, i, vis);
+}
+hipError_t launch_diag_fused(const DevScene& sc, const DiagArgs& a, bool visible, int guards, bool mesh_nearest,
+                             hipStream_t st) {
+    if (a.n <= 0) return hipSuccess;
+    const int cfg = guards == 1 ? 4 : guards == 2 ? (mesh_nearest ? 6 : 5) : (sc.compact ? 1 : 0) | (mesh_nearest ? 2 : 0);
+    const dim3 grid((unsigned)((a.n + 255) / 256)), block(256);
+    const int vis = visible ? 1 : 0;
+    switch (cfg) {  // one kernel per instance: each holds one copy of the walks
+        case 0: hipLaunchKernelGGL(k_diag_fused<1>, grid, block, 0, st, sc, a, vis); break;
+        case 1: hipLaunchKernelGGL(k_diag_fused<9>, grid, block, 0, st, sc, a, vis); break;
+        case 2: hipLaunchKernelGGL(k_diag_fused<17>, grid, block, 0, st, sc, a, vis); break;
+        case 3: hipLaunchKernelGGL(k_diag_fused<25>, grid, block, 0, st, sc, a, vis); break;
+        case 4: hipLaunchKernelGGL(k_diag_fused<8>, grid, block, 0, st, sc, a, vis); break;
+        case 5: hipLaunchKernelGGL((k_diag_fused<9 | kCfgGuards1>), grid, block, 0, st, sc, a, vis); break;
+        default: hipLaunchKernelGGL((k_diag_fused<25 | kCfgGuards1>), grid, block, 0, st, sc, a, vis); break;
+    }
+    return hipGetLastError();
 }
 
 thread_local TailPlan t_tail_plan;

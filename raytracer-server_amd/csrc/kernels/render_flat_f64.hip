@@ -30,6 +30,7 @@
 #include "../device/integrator_f64.h"
 #include "kernels.h"
 #include "megakernel_common.h"
+#include "diag_queries.h"
 
 namespace rt {
 using namespace f64;
@@ -921,6 +922,67 @@ hipError_t launch_megakernel_flat_f64(const DevScene& sc, const RenderArgs& a_in
     }
 #undef RT_FLAT_CASE
     launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
+    return hipGetLastError();
+}
+
+// rt_diag_trace / rt_diag_visible, the flat query pool's split of a query (RenderArgs::all_flat scenes): the
+// analytic part, mesh_near_mask, then flat_query for each near mesh, merged in gen order by consider as
+// k_megakernel_fpool_f64 merges its answered queries (closest), or occluded by any blocking hit (shadow).
+// flat_query reads its mesh through scalar loads and takes wave votes, so the loop over the meshes is uniform
+// (kernel-argument bounds) and a lane only takes part in the query of a mesh whose bit it holds.
+__global__ __launch_bounds__(kBlk) void k_diag_flat(DevScene sc, DiagArgs a, int vis) {
+    using C = Cfg<9>;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    Ray r;
+    HitRec h{0.0, -1, -1};
+    double dist = 0.0;
+    bool clear = true;
+    RayInv inv;
+    if (vis) {
+        V3 y;
+        r = diag_segment(a, i, &y, &dist);
+        clear = visible_analytic<C>(sc, y, r, dist);
+        inv = make_inv(r.d);
+    } else {
+        r = diag_ray(a, i);
+        inv = make_inv(r.d);
+        h = trace_analytic<C>(sc, r, inv);
+    }
+    const uint32_t near = mesh_near_mask<C>(sc, r, inv, vis ? dist : (h.obj >= 0 ? h.t : INFINITY));
+    const uint32_t want = clear ? near : 0u;
+    double qt[kFlatMeshes];
+    int qp[kFlatMeshes];
+    bool occluded = !clear;
+#pragma unroll
+    for (int m = 0; m < kFlatMeshes; ++m) {
+        qt[m] = 0.0;
+        qp[m] = -1;
+        if (m < sc.n_meshes && ((want >> m) & 1u)) {
+            double t = 0.0;
+            int prim = -1;
+            const bool hit = flat_query(sc, m, r, &t, &prim);
+            qt[m] = t;
+            qp[m] = hit ? prim : -1;
+            occluded |= vis && hit && !(t + 0.001 >= dist);
+        }
+    }
+    if (vis) {
+        diag_store_vis(a, i, !occluded, near);
+        return;
+    }
+    CTab* T = tables(sc);
+    for (int g = 0; g < T->n_gen; ++g) {
+        const int mm = T->gen_mesh[g];
+#pragma unroll
+        for (int m = 0; m < kFlatMeshes; ++m)
+            if (mm == m && ((want >> m) & 1u) && qp[m] >= 0) consider(h, qt[m], T->gen_idx[g], qp[m]);
+    }
+    diag_store_hit(sc, a, i, r, h, near);
+}
+hipError_t launch_diag_flat(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st) {
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_diag_flat, dim3((unsigned)((a.n + kBlk - 1) / kBlk)), dim3(kBlk), 0, st, sc, a, visible ? 1 : 0);
     return hipGetLastError();
 }
 

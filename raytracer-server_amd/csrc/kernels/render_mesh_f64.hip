@@ -10,6 +10,7 @@
 #include "../device/integrator_f64.h"
 #include "kernels.h"
 #include "megakernel_common.h"
+#include "diag_queries.h"
 
 namespace rt {
 using namespace f64;
@@ -1301,6 +1302,59 @@ hipError_t launch_megakernel_mesh_f64(const DevScene& sc, const RenderArgs& a, d
 #undef RT_MMB_CASE
 #undef RT_MM_CASE
 #undef RT_MM_AB
+    return hipGetLastError();
+}
+
+// rt_diag_trace / rt_diag_visible, the roles and walk pools' split of a query (compact scenes with slot tables):
+// the analytic part (trace_analytic / visible_analytic), mesh_near_mask at the analytic hit's t (closest) or
+// |y - x| (shadow), then the slot walk of each near mesh in gen order, begun as pool_round begins it
+// (next_mesh_walk_near: no second cull) with an LDS ancestor column, and merged by consider (closest) or
+// ended by the first blocking hit (shadow). One lane per query, walks run to their end.
+__global__ __launch_bounds__(256) void k_diag_slots(DevScene sc, DiagArgs a, int vis) {
+    using C = Cfg<9>;
+    __shared__ int32_t s_anc[kSlotAncLevels * 256];
+    LdsAncI32* anc = (LdsAncI32*)s_anc + threadIdx.x;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    Ray r;
+    HitRec h{0.0, -1, -1};
+    double dist = 0.0;
+    bool clear = true;  // shadow: the analytic objects let the segment through
+    RayInv inv;
+    if (vis) {
+        V3 y;
+        r = diag_segment(a, i, &y, &dist);
+        clear = visible_analytic<C>(sc, y, r, dist);
+        inv = make_inv(r.d);
+    } else {
+        r = diag_ray(a, i);
+        inv = make_inv(r.d);
+        h = trace_analytic<C>(sc, r, inv);
+    }
+    const uint32_t near = mesh_near_mask<C>(sc, r, inv, vis ? dist : (h.obj >= 0 ? h.t : INFINITY));
+    bool occluded = !clear;
+    if (clear && near) {
+        OctWalk w;
+        int g = -1, mi = -1;
+        while (!occluded) {
+            const double tmax = vis ? dist : (h.obj >= 0 ? h.t : INFINITY);
+            if (!next_mesh_walk_near<C, true>(sc, r, inv, tmax, g, mi, w, near)) break;
+            double t;
+            int prim, st;
+            while ((st = walk_step<true, 256, RT_WALK_HOIST>(sc, sc.meshes[mi], r, inv, w, &t, &prim, anc)) == WALK_RUN) {
+            }
+            if (st == WALK_HIT) {
+                if (vis) occluded = !(t + 0.001 >= dist);  // mutually_visible's ERR_MARGIN
+                else consider(h, t, tables(sc)->gen_idx[g], prim);
+            }
+        }
+    }
+    if (vis) diag_store_vis(a, i, !occluded, near);
+    else diag_store_hit(sc, a, i, r, h, near);
+}
+hipError_t launch_diag_slots(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st) {
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_diag_slots, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, sc, a, visible ? 1 : 0);
     return hipGetLastError();
 }
 

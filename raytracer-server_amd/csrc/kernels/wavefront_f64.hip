@@ -25,6 +25,7 @@
 
 #include "../device/integrator_f64.h"
 #include "wavefront.h"
+#include "diag_queries.h"
 #include "../ab_knobs.h"
 
 namespace rt {
@@ -619,6 +620,59 @@ int wavefront_render_f64(const DevScene& sc, const RenderArgs& a_in, Workspace& 
         stats->kernel_launches[1] = iters;
     }
     return RT_OK;
+}
+
+// rt_diag_trace / rt_diag_visible, the wavefront's split of a query (compact scenes): k_wf_extend's analytic
+// part and mesh_candidate (closest), shade_vertex's visible_analytic and near mask (shadow); a candidate then
+// walks every mesh object in gen order as ClosestQuery / ShadowQuery do: walk_begin<false> with its own f64
+// cull at the closest t so far (closest) or |y - x| (shadow), walk_step<false> to the walk's end.
+__global__ __launch_bounds__(kBlock) void k_diag_kids(DevScene sc, DiagArgs a, int vis) {
+    using C = Cfg<9>;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    Ray r;
+    HitRec h{0.0, -1, -1};
+    double dist = 0.0;
+    bool clear = true;
+    RayInv inv;
+    if (vis) {
+        V3 y;
+        r = diag_segment(a, i, &y, &dist);
+        clear = visible_analytic<C>(sc, y, r, dist);
+        inv = make_inv(r.d);
+    } else {
+        r = diag_ray(a, i);
+        inv = make_inv(r.d);
+        h = trace_analytic<C>(sc, r, inv);
+    }
+    const uint32_t near = mesh_near_mask<C>(sc, r, inv, vis ? dist : (h.obj >= 0 ? h.t : INFINITY));
+    bool occluded = !clear;
+    if (clear && near) {
+        OctWalk w;
+        for (int g = 0; g < tables(sc)->n_gen && !occluded; ++g) {
+            const int idx = tables(sc)->gen_idx[g];
+            const DevObject& o = sc.objects[idx];
+            if (o.geom != GEOM_MESH) continue;
+            const DevMesh& m = sc.meshes[o.mesh];
+            if (!walk_begin<false>(sc, m, r, inv, vis ? dist : (h.obj >= 0 ? h.t : INFINITY), w)) continue;
+            double t;
+            int prim, st;
+            while ((st = walk_step<false>(sc, m, r, inv, w, &t, &prim)) == WALK_RUN) {
+            }
+            if (st == WALK_HIT) {
+                if (vis) occluded = !(t + 0.001 >= dist);  // mesh_occludes / mutually_visible's ERR_MARGIN
+                else consider(h, t, idx, prim);
+            }
+        }
+    }
+    if (vis) diag_store_vis(a, i, !occluded, near);
+    else diag_store_hit(sc, a, i, r, h, near);
+}
+hipError_t launch_diag_kids(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st) {
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_diag_kids, dim3((unsigned)((a.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, sc, a,
+                       visible ? 1 : 0);
+    return hipGetLastError();
 }
 
 }  // namespace rt

@@ -13,6 +13,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/rt_diag.h"
 #include "../../include/rt_ffi.h"
 #include "ab_knobs.h"
 #include "device/scene_layout.h"
@@ -1661,6 +1662,111 @@ int rt_denoise(int32_t device, int32_t width, int32_t height, const double* sub,
     (void)hipFree(buf);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_denoise: ") + hipGetErrorString(e));
     return rc < 0 ? fail(rc, err) : rc;
+}
+
+// Batch query diagnostics (include/rt_diag.h, kernels/diag_queries.h) -------------------------------------
+
+namespace {
+
+// The arguments of rt_diag_trace / rt_diag_visible that need no device: form, flags and what the form asks of
+// the scene.
+int check_diag(const char* who, const rt_scene* s, int32_t form, uint32_t flags, int64_t n, bool ptrs) {
+    if (!s || !ptrs) return fail(RT_E_INVAL, std::string(who) + ": null argument");
+    if (n < 0) return fail(RT_E_INVAL, std::string(who) + ": n must be >= 0");
+    if (form < RT_DIAG_FUSED || form > RT_DIAG_FUSED_G1) return fail(RT_E_INVAL, std::string(who) + ": unknown form");
+    if (flags & ~RT_FLAG_MESH_NEAREST) return fail(RT_E_INVAL, std::string(who) + ": unknown flag");
+    if (flags && form != RT_DIAG_FUSED && form != RT_DIAG_FUSED_G1)
+        return fail(RT_E_INVAL, std::string(who) + ": RT_FLAG_MESH_NEAREST needs a fused form");
+    int32_t compact = 0;
+    {
+        rt::CompactTab tab;
+        fill_compact(s->packed, &tab, &compact);
+    }
+    const bool meshes = !s->host.meshes.empty();
+    if (form == RT_DIAG_FUSED_G0 && (meshes || !compact))
+        return fail(RT_E_INVAL, std::string(who) + ": the mesh-free fused form needs a compact scene without meshes");
+    if (form >= RT_DIAG_SPLIT_SLOTS && (!meshes || !compact))
+        return fail(RT_E_INVAL, std::string(who) + ": this form needs a compact scene with meshes");
+    if (form == RT_DIAG_SPLIT_SLOTS && s->packed.slots.empty())
+        return fail(RT_E_INVAL, std::string(who) + ": the slot-walk form needs the scene's slot tables");
+    if (form == RT_DIAG_SPLIT_FLAT) {
+        bool all_flat = s->packed.meshes.size() <= (size_t)rt::kFlatMeshes;
+        for (const auto& dm : s->packed.meshes) all_flat &= dm.flat != 0;
+        if (!all_flat) return fail(RT_E_INVAL, std::string(who) + ": the flat-query form needs flat octrees only");
+    }
+    return RT_OK;
+}
+
+// Uploads the inputs, runs the form's kernel, reads back: in[2] are [n][3] doubles; outs: (host, bytes per query).
+struct DiagOut {
+    void* host;
+    size_t per;
+    void** dev;
+};
+int diag_run(const char* who, const rt_scene* scene, int32_t device, int32_t form, uint32_t flags, bool visible,
+             rt::DiagArgs& a, const double* in0, const double* in1, const double** d_in0, const double** d_in1,
+             DiagOut* outs, int n_outs) {
+    HIP_TRY(hipSetDevice(device));
+    rt::DevScene ds;
+    int rc = upload(const_cast<rt_scene*>(scene), device, &ds);
+    if (rc != RT_OK) return rc;
+    const size_t n = (size_t)a.n, v3 = n * 3 * sizeof(double);
+    size_t total = 2 * v3;
+    for (int k = 0; k < n_outs; ++k) total += align_up(outs[k].host ? n * outs[k].per : 0, 16);
+    char* buf = nullptr;
+    HIP_TRY(hipMalloc((void**)&buf, total));
+    *d_in0 = (const double*)buf;
+    *d_in1 = (const double*)(buf + v3);
+    size_t off = 2 * v3;
+    for (int k = 0; k < n_outs; ++k) {
+        *outs[k].dev = outs[k].host ? (void*)(buf + off) : nullptr;
+        off += align_up(outs[k].host ? n * outs[k].per : 0, 16);
+    }
+    hipError_t e = hipMemcpy(buf, in0, v3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + v3, in1, v3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(buf + 2 * v3, 0, total - 2 * v3);
+    if (e == hipSuccess) {
+        if (form == RT_DIAG_FUSED || form == RT_DIAG_FUSED_G0 || form == RT_DIAG_FUSED_G1)
+            e = rt::launch_diag_fused(ds, a, visible, form == RT_DIAG_FUSED_G0 ? 1 : form == RT_DIAG_FUSED_G1 ? 2 : 0,
+                                      (flags & RT_FLAG_MESH_NEAREST) != 0, nullptr);
+        else if (form == RT_DIAG_SPLIT_SLOTS) e = rt::launch_diag_slots(ds, a, visible, nullptr);
+        else if (form == RT_DIAG_SPLIT_KIDS) e = rt::launch_diag_kids(ds, a, visible, nullptr);
+        else e = rt::launch_diag_flat(ds, a, visible, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int k = 0; k < n_outs && e == hipSuccess; ++k)
+        if (outs[k].host) e = hipMemcpy(outs[k].host, *outs[k].dev, n * outs[k].per, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return RT_OK;
+}
+
+}  // namespace
+
+int rt_diag_trace(const rt_scene* scene, int32_t device, int32_t form, uint32_t flags, int64_t n, const double* o,
+                  const double* d, double* t, int32_t* obj, int32_t* prim, double* pos, double* nrm) {
+    int rc = check_diag("rt_diag_trace", scene, form, flags, n, o && d && t && obj && prim && pos && nrm);
+    if (rc != RT_OK || n == 0) return rc;
+    if ((rc = need_device("rt_diag_trace", device)) != RT_OK) return rc;
+    rt::DiagArgs a{};
+    a.n = (long)n;
+    DiagOut outs[5] = {{t, sizeof(double), (void**)&a.t},
+                       {obj, sizeof(int32_t), (void**)&a.obj},
+                       {prim, sizeof(int32_t), (void**)&a.prim},
+                       {pos, 3 * sizeof(double), (void**)&a.pos},
+                       {nrm, 3 * sizeof(double), (void**)&a.nrm}};
+    return diag_run("rt_diag_trace", scene, device, form, flags, false, a, o, d, &a.a, &a.b, outs, 5);
+}
+
+int rt_diag_visible(const rt_scene* scene, int32_t device, int32_t form, uint32_t flags, int64_t n, const double* x,
+                    const double* y, uint8_t* vis, uint32_t* near_mask) {
+    int rc = check_diag("rt_diag_visible", scene, form, flags, n, x && y && vis);
+    if (rc != RT_OK || n == 0) return rc;
+    if ((rc = need_device("rt_diag_visible", device)) != RT_OK) return rc;
+    rt::DiagArgs a{};
+    a.n = (long)n;
+    DiagOut outs[2] = {{vis, sizeof(uint8_t), (void**)&a.vis}, {near_mask, sizeof(uint32_t), (void**)&a.near_mask}};
+    return diag_run("rt_diag_visible", scene, device, form, flags, true, a, x, y, &a.a, &a.b, outs, 2);
 }
 
 }  // extern "C"

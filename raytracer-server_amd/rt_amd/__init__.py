@@ -27,6 +27,8 @@ FLAG_MIS = 1 << 0
 FLAG_MEGAKERNEL = 1 << 1
 FLAG_FP32 = 1 << 2
 FLAG_MESH_NEAREST = 1 << 3  # Mesh::intersect without the octree (geometry.rs:886-903), BVH on the device
+# query forms of Scene.diag_trace / diag_visible (include/rt_diag.h RT_DIAG_*)
+DIAG_FUSED, DIAG_FUSED_G0, DIAG_SPLIT_SLOTS, DIAG_SPLIT_KIDS, DIAG_SPLIT_FLAT, DIAG_FUSED_G1 = range(6)
 
 BRDF_DIFFUSE, BRDF_SPECULAR, BRDF_PHONG = 0, 1, 2
 GEOM_SPHERE, GEOM_PLANE, GEOM_MESH = 0, 1, 2
@@ -129,6 +131,11 @@ def _load():
         L.rt_debug_wave_times.argtypes = [P(ctypes.c_ulonglong), ctypes.c_int]
     if hasattr(L, "rt_debug_last_split"):
         L.rt_debug_last_split.argtypes = [P(ctypes.c_longlong)]
+    if hasattr(L, "rt_diag_trace"):
+        D = ctypes.c_double
+        L.rt_diag_trace.argtypes = [vp, I, I, ctypes.c_uint32, ctypes.c_int64, P(D), P(D), P(D), P(I), P(I), P(D), P(D)]
+        L.rt_diag_visible.argtypes = [vp, I, I, ctypes.c_uint32, ctypes.c_int64, P(D), P(D), P(ctypes.c_uint8),
+                                      P(ctypes.c_uint32)]
     return L
 
 
@@ -258,6 +265,35 @@ class Scene:
         _check(lib.rt_trace_rays_flags(self._h, device, FLAG_MESH_NEAREST if mesh_nearest else 0, n, _ptr(o, D),
                                        _ptr(d, D), _ptr(t, D), _ptr(ids, ctypes.c_int32), _ptr(pos, D), _ptr(nrm, D)))
         return t, ids, pos, nrm
+
+    def diag_trace(self, origins, dirs, form=0, device=0, mesh_nearest=False):
+        """Scene::trace_ray per ray through the query code of one kernel family (rt_diag.h rt_diag_trace,
+        form = DIAG_*): t, object (-1: miss), triangle (-1: none), pos, normal."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        t = np.zeros(n)
+        ids = np.zeros(n, dtype=np.int32)
+        prim = np.zeros(n, dtype=np.int32)
+        pos = np.zeros((n, 3))
+        nrm = np.zeros((n, 3))
+        D, I = ctypes.c_double, ctypes.c_int32
+        _check(lib.rt_diag_trace(self._h, device, form, FLAG_MESH_NEAREST if mesh_nearest else 0, n, _ptr(o, D),
+                                 _ptr(d, D), _ptr(t, D), _ptr(ids, I), _ptr(prim, I), _ptr(pos, D), _ptr(nrm, D)))
+        return t, ids, prim, pos, nrm
+
+    def diag_visible(self, x, y, form=0, device=0, mesh_nearest=False):
+        """Scene::mutually_visible per segment through the query code of one kernel family (rt_diag.h
+        rt_diag_visible): visible (bool), and the split forms' mask of meshes near the segment (0 otherwise)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, 3)
+        n = x.shape[0]
+        vis = np.zeros(n, dtype=np.uint8)
+        near = np.zeros(n, dtype=np.uint32)
+        D = ctypes.c_double
+        _check(lib.rt_diag_visible(self._h, device, form, FLAG_MESH_NEAREST if mesh_nearest else 0, n, _ptr(x, D),
+                                   _ptr(y, D), _ptr(vis, ctypes.c_uint8), _ptr(near, ctypes.c_uint32)))
+        return vis.astype(bool), near
 
 
 def make_params(width, height, spp, seed=0x5EED, tile=None, flags=0, device=0, row_step=1):

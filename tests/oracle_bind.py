@@ -56,6 +56,8 @@ def lib():
         L.orc_draws.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                 ctypes.c_int, _D]
         L.orc_trace.argtypes = [ctypes.c_void_p, ctypes.c_int64, _D, _D, _D, _I32, _D, _D]
+        L.orc_visible.restype = None
+        L.orc_visible.argtypes = [ctypes.c_void_p, ctypes.c_int64, _D, _D, _U8]
         L.orc_scene_set_mesh_accel.restype = None
         L.orc_scene_set_mesh_accel.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.orc_render.restype = ctypes.c_int64
@@ -195,6 +197,14 @@ class OracleScene:
         nrm = np.zeros((n, 3))
         lib().orc_trace(self.h, n, _dp(o), _dp(d), _dp(t), ids.ctypes.data_as(_I32), _dp(pos), _dp(nrm))
         return t, ids, pos, nrm
+
+    def visible(self, x, y):
+        """Scene::mutually_visible (scene.rs:258-270) per segment x -> y: a bool array."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(x.shape[0], dtype=np.uint8)
+        lib().orc_visible(self.h, x.shape[0], _dp(x), _dp(y), out.ctypes.data_as(_U8))
+        return out.astype(bool)
 
     def render(self, width, height, spp, seed, tile=None, mis=False, threads=None, want_sub=True):
         x0, y0, tw, th = tile if tile is not None else (0, 0, width, height)
