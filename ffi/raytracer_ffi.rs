@@ -204,6 +204,40 @@ extern "C" {
         sigma_n: f32, sigma_z: f32, sigma_a: f32, rgb_out: *mut u8, lin_out: *mut f32, stream: *mut c_void,
     ) -> c_int;
 
+    /// Progressive accumulation (rt_ffi.h). The accumulator handle is an opaque pointer; one call
+    /// at a time per accumulator. `rt_accum_create` makes no device call.
+    pub fn rt_accum_create(device: i32, width: i32, height: i32, out: *mut *mut c_void) -> c_int;
+    pub fn rt_accum_destroy(accum: *mut c_void);
+    pub fn rt_accum_reset(accum: *mut c_void) -> c_int;
+    /// `info`: K (passes), N (samples per subpixel), width, height.
+    pub fn rt_accum_info(accum: *const c_void, info: *mut i64 /* [4] */) -> c_int;
+    /// Renders `params` (the accumulator's whole frame, spp >= 4) and merges it; `RT_CANCELLED` leaves the
+    /// accumulator untouched.
+    pub fn rt_accum_add(
+        accum: *mut c_void, scene: *const RtScene, params: *const RtRenderParams, cancel: *const i32,
+        stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// Merges a pass rendered elsewhere: `sub` width * height * 12 f64 (host), `n` >= 1 samples per subpixel.
+    pub fn rt_accum_add_sub(accum: *mut c_void, sub: *const f64, n: i32) -> c_int;
+    pub fn rt_accum_add_sub_device(accum: *mut c_void, d_sub: *const c_void, n: i32, stream: *mut c_void) -> c_int;
+    /// The accumulated frame; any output may be null. `var_out` (width * height * 4 f32) needs two passes.
+    pub fn rt_accum_resolve(accum: *mut c_void, sub_out: *mut f64, var_out: *mut f32, rgb_out: *mut u8) -> c_int;
+    pub fn rt_accum_resolve_device(
+        accum: *mut c_void, d_sub: *mut c_void, d_var: *mut c_void, d_rgb: *mut c_void, stream: *mut c_void,
+    ) -> c_int;
+    /// `rt_denoise` with the colour term scaled by the pixel's variance (`var`: `rt_accum_resolve`'s `var_out`);
+    /// `var_out` (nullable): width * height f32, the filtered variance.
+    pub fn rt_denoise_var(
+        device: i32, width: i32, height: i32, sub: *const f64, feat: *const f32, var: *const f32, levels: i32,
+        sigma_c: f32, sigma_n: f32, sigma_z: f32, sigma_a: f32, rgb_out: *mut u8, lin_out: *mut f32,
+        var_out: *mut f32,
+    ) -> c_int;
+    pub fn rt_denoise_var_device(
+        device: i32, width: i32, height: i32, sub: *const f64, feat: *const f32, var: *const f32, levels: i32,
+        sigma_c: f32, sigma_n: f32, sigma_z: f32, sigma_a: f32, rgb_out: *mut u8, lin_out: *mut f32,
+        var_out: *mut f32, stream: *mut c_void,
+    ) -> c_int;
+
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_abi_version() -> c_int;
     pub fn rt_device_count() -> c_int;

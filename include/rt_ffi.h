@@ -14,6 +14,8 @@
  *                          RenderJob::run, server.rs:165-168), host gather
  *   rt_trace_rays       <- Scene::trace_ray                  src/scene.rs:272-289 (batch form, for parity tests)
  *   rt_render_features, rt_denoise: no counterpart in the reference (denoised previews at low spp)
+ *   rt_accum_*, rt_denoise_var: no counterpart either (progressive refinement: merged passes, their variance, and
+ *                          a filter guided by it)
  *
  * Conventions (mirroring the reference's):
  *   - a scene is immutable after creation and may be shared by concurrent rt_render calls
@@ -40,7 +42,7 @@ extern "C" {
 
 #define RT_ABI_VERSION 3  /* 2: rt_render_params.row_step; 3: rt_render_multi. The denoised-preview entry points
                              (rt_render_features*, rt_denoise*) are additive: no struct or existing call changed, so
-                             the version stays 3 */
+                             the version stays 3; likewise progressive accumulation (rt_accum_*, rt_denoise_var*) */
 
 /* return codes */
 #define RT_OK 0
@@ -207,6 +209,70 @@ int rt_denoise(int32_t device, int32_t width, int32_t height, const double* sub,
 int rt_denoise_device(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
                       int32_t levels, float sigma_c, float sigma_n, float sigma_z, float sigma_a, uint8_t* rgb_out,
                       float* lin_out, void* stream);
+
+/* Progressive accumulation -------------------------------------------------------- */
+/* An accumulator merges render passes of one width x height frame on one device and estimates each pixel's variance
+ * from the pass-to-pass scatter. Its handle is an opaque pointer (void*: made by rt_accum_create, released by
+ * rt_accum_destroy). It is not thread-safe: one call at a time per accumulator. Per subpixel and channel
+ * (width * height * 12) it holds two f64 sums on the device,
+ *   S = sum_k n_k m_k        Q = sum_k n_k m_k^2
+ * m_k: pass k's subpixel mean (rt_render's sub_out, before the clamp), n_k = floor(spp_k / 4) its samples per
+ * subpixel; on the host K (passes) and N = sum_k n_k. That is 192 bytes per pixel (398 MB at 1920 x 1080), allocated
+ * by the first pass, plus a staging area of 115 bytes per pixel (a pass's sub, a variance image, an RGB8 frame:
+ * 238 MB at 1920 x 1080) allocated by the first call that needs one (rt_accum_add, the host forms, an RGB8 resolve
+ * without a sub buffer). rt_accum_create itself makes no device call.
+ * Arithmetic, fixed so that a numpy restatement gives the same bits (no FMA contraction): per element
+ *   S += (double)n * m;  Q += ((double)n * m) * m;      the first pass after create or reset stores without reading.
+ * Every call waits for the device work it enqueued before it returns. */
+int rt_accum_create(int32_t device, int32_t width, int32_t height, void** out);
+void rt_accum_destroy(void* accum);
+/* Forgets every pass (K = N = 0); the device memory is kept. */
+int rt_accum_reset(void* accum);
+/* info[4] = K, N, width, height */
+int rt_accum_info(const void* accum, int64_t info[4]);
+/* Renders `params` (rt_render's enqueue path: every flag passes through, the caller chooses the seed) into the
+ * accumulator's staging buffer and merges it with n = floor(spp / 4). params must be the accumulator's whole frame:
+ * its width, height and device, x0 = y0 = 0, tile_w = width, tile_h = height, row_step 0 or 1, spp >= 4; RT_E_INVAL
+ * otherwise, before any device call. cancel and stats as in rt_render; a cancelled pass returns RT_CANCELLED and
+ * leaves S, Q, K and N untouched. */
+int rt_accum_add(void* accum, const rt_scene* scene, const rt_render_params* params, const volatile int32_t* cancel,
+                 rt_render_stats* stats);
+/* Merges a pass rendered elsewhere (another device's or host's rt_render sub_out of the whole frame; synthetic passes
+ * in tests): sub is width * height * 12 f64 on the host, n >= 1 its samples per subpixel. */
+int rt_accum_add_sub(void* accum, const double* sub, int32_t n);
+/* The same from a device buffer of the accumulator's device (16-byte aligned), enqueued on `stream`. */
+int rt_accum_add_sub_device(void* accum, const void* d_sub, int32_t n, void* stream);
+/* The accumulated frame (K >= 1, else RT_E_INVAL); any output may be NULL.
+ *   sub_out: width * height * 12 f64, S / N (IEEE division)
+ *   rgb_out: width * height * 3 u8, sub_out through rt_render's clamp, average, gamma and `as u8` (k_finalize_f64)
+ *   var_out: width * height * 4 floats (v_r, v_g, v_b, v_r + v_g + v_b); needs K >= 2, else RT_E_INVAL. The variance
+ *            of the clamped pixel colour of the accumulated frame, through the clamp by the delta method: per
+ *            subpixel j and channel, m = S / N, vs = max(0, Q / N - m m) / (K - 1);
+ *            v_ch = (sum_{j = 0..3} [0 < m_j < 1] vs_j) / 16, summed in j order in f64; [3] = (v_r + v_g) + v_b in
+ *            f64; each rounded to f32. */
+int rt_accum_resolve(void* accum, double* sub_out, float* var_out, uint8_t* rgb_out);
+/* The same into device buffers of the accumulator's device (d_sub and d_var 16-byte aligned), enqueued on `stream`. */
+int rt_accum_resolve_device(void* accum, void* d_sub, void* d_var, void* d_rgb, void* stream);
+
+/* Variance-guided a-trous filter: rt_denoise with the colour term scaled by the pixel's variance.
+ * sub, feat, levels, sigma_n, sigma_z, sigma_a, rgb_out, lin_out: as rt_denoise. var: width * height * 4 floats as
+ * rt_accum_resolve's var_out; only [3] is used, v0_p = max(var[p][3], 0). c0 as rt_denoise. Level i, s = 2^i, the
+ * taps, their order and h of rt_denoise:
+ *   g_p  = sum k[dx] k[dy] v_q / sum k[dx] k[dy],   q = p + s (dx, dy), dx, dy in -1..1, inside the image,
+ *          k = (1/4, 1/2, 1/4), row-major (dy, dx) order
+ *   E    = |c_p - c_q|^2 * (1 / (sigma_c^2 g_p + 1e-10)) + the normal, depth and albedo / coverage terms of rt_denoise
+ *   w    = h[dx + 2] h[dy + 2] exp(-E),   c'_p = sum_q w c_q / sum_q w,   v'_p = sum_q w^2 v_q / (sum_q w)^2
+ * (no 2^-i on sigma_c: the variance shrinks by itself; f32 arithmetic). sigma_c <= 0 drops the colour term; levels = 0
+ * is rt_denoise's pass-through, byte for byte. var_out (optional): width * height floats, the filtered variance. */
+int rt_denoise_var(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
+                   const float* var, int32_t levels, float sigma_c, float sigma_n, float sigma_z, float sigma_a,
+                   uint8_t* rgb_out, float* lin_out, float* var_out);
+/* The same on device buffers of `device` (sub, feat and var 16-byte aligned), enqueued on `stream`; the call waits
+ * for the filter. Scratch as rt_denoise_device (32 bytes per pixel: the variance rides in the colour's fourth
+ * component). */
+int rt_denoise_var_device(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
+                          const float* var, int32_t levels, float sigma_c, float sigma_n, float sigma_z,
+                          float sigma_a, uint8_t* rgb_out, float* lin_out, float* var_out, void* stream);
 
 const char* rt_last_error(void);
 int rt_abi_version(void);

@@ -39,4 +39,11 @@ hipError_t launch_atrous(int width, int height, const double* sub, const float* 
                          float sigma_n, float sigma_z, float sigma_a, void* scratch, uint8_t* rgb, float* lin,
                          hipStream_t st);
 
+// The variance-guided filter (rt_denoise_var*): launch_atrous with var[pix][4] f32 (only [3] is read)
+// scaling the colour term, and the filtered variance vout[pix] f32 (nullable). The same scratch: the variance rides
+// in the colour entries' fourth component. AtrousArgs::inv_c carries sigma_c^2 here (0 drops the colour term).
+hipError_t launch_atrous_var(int width, int height, const double* sub, const float* feat, const float* var,
+                             int levels, float sigma_c, float sigma_n, float sigma_z, float sigma_a, void* scratch,
+                             uint8_t* rgb, float* lin, float* vout, hipStream_t st);
+
 }  // namespace rt

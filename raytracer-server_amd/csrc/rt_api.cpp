@@ -18,6 +18,7 @@
 #include "ab_knobs.h"
 #include "device/scene_layout.h"
 #include "host/scene_host.hpp"
+#include "kernels/accum.h"
 #include "kernels/denoise.h"
 #include "kernels/kernels.h"
 #include "kernels/wavefront.h"
@@ -1661,6 +1662,338 @@ int rt_denoise(int32_t device, int32_t width, int32_t height, const double* sub,
     }
     (void)hipFree(buf);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_denoise: ") + hipGetErrorString(e));
+    return rc < 0 ? fail(rc, err) : rc;
+}
+
+// Progressive accumulation ----------------------------------------------------------------
+
+// The device memory comes lazily (rt_ffi.h): the sums with the first pass, the staging area (a pass's sub, a variance
+// image, an RGB8 frame) with the first call that needs one. rt_accum_add and the host forms run on a stream of their
+// own that lives for the call, as rt_render's does.
+struct rt_accum {
+    int32_t device = 0, width = 0, height = 0;
+    int64_t K = 0, N = 0;
+    double* S = nullptr;
+    double* Q = nullptr;
+    char* stage = nullptr;
+    size_t npix() const { return (size_t)width * height; }
+    size_t sub_bytes() const { return npix() * 12 * sizeof(double); }
+    double* stage_sub() const { return (double*)stage; }
+    float* stage_var() const { return (float*)(stage + sub_bytes()); }
+    uint8_t* stage_rgb() const { return (uint8_t*)(stage + sub_bytes() + npix() * 4 * sizeof(float)); }
+};
+
+namespace {
+
+int oom_or_hip(hipError_t e, const char* what) {
+    return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// A stream for one call: waited for and destroyed when the call returns.
+struct CallStream {
+    hipStream_t st = nullptr;
+    CallStream() = default;
+    CallStream(const CallStream&) = delete;
+    CallStream& operator=(const CallStream&) = delete;
+    hipError_t init() { return hipStreamCreateWithFlags(&st, hipStreamNonBlocking); }
+    ~CallStream() {
+        if (!st) return;
+        (void)hipStreamSynchronize(st);
+        (void)hipStreamDestroy(st);
+    }
+};
+
+// Selects the accumulator's device and makes what the call needs of its sums and staging area.
+int accum_ready(rt_accum* a, bool sums, bool stage) {
+    HIP_TRY(hipSetDevice(a->device));
+    hipError_t e = hipSuccess;
+    if (sums && !a->S) {
+        e = hipMalloc((void**)&a->S, 2 * a->sub_bytes());
+        if (e == hipSuccess) a->Q = a->S + a->npix() * 12;
+        else a->S = nullptr;
+    }
+    if (e == hipSuccess && stage && !a->stage) {
+        e = hipMalloc((void**)&a->stage, a->sub_bytes() + a->npix() * 4 * sizeof(float) + align_up(a->npix() * 3, 16));
+        if (e != hipSuccess) a->stage = nullptr;
+    }
+    if (e != hipSuccess) return oom_or_hip(e, "rt_accum buffers");
+    return RT_OK;
+}
+
+// Merges the pass in d_sub on `st`, waits for it and counts it.
+int accum_merge(rt_accum* a, const double* d_sub, int32_t n, hipStream_t st) {
+    hipError_t e = rt::launch_accum_add(a->S, a->Q, d_sub, (long)a->npix(), n, a->K == 0, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum merge: ") + hipGetErrorString(e));
+    a->K += 1;
+    a->N += n;
+    return RT_OK;
+}
+
+int check_accum_add(const rt_accum* a, const rt_scene* scene, const rt_render_params* p) {
+    if (!a || !scene || !p) return fail(RT_E_INVAL, "rt_accum_add: null argument");
+    if (p->width != a->width || p->height != a->height || p->x0 != 0 || p->y0 != 0 || p->tile_w != a->width ||
+        p->tile_h != a->height)
+        return fail(RT_E_INVAL, "rt_accum_add: params must be the accumulator's whole frame");
+    if (p->row_step < 0 || p->row_step > 1) return fail(RT_E_INVAL, "rt_accum_add: row_step must be 0 or 1");
+    if (p->spp < 4) return fail(RT_E_INVAL, "rt_accum_add: spp must be >= 4");
+    if (p->device != a->device) return fail(RT_E_INVAL, "rt_accum_add: params->device is not the accumulator's device");
+    return check_params(p);
+}
+
+int check_accum_sub(const char* who, const rt_accum* a, const void* sub, int32_t n) {
+    if (!a || !sub) return fail(RT_E_INVAL, std::string(who) + ": null argument");
+    if (n < 1) return fail(RT_E_INVAL, std::string(who) + ": n must be >= 1");
+    return RT_OK;
+}
+
+int check_accum_resolve(const char* who, const rt_accum* a, const void* var) {
+    if (!a) return fail(RT_E_INVAL, std::string(who) + ": null argument");
+    if (a->K < 1) return fail(RT_E_INVAL, std::string(who) + ": no pass accumulated");
+    if (var && a->K < 2) return fail(RT_E_INVAL, std::string(who) + ": the variance needs at least two passes");
+    return RT_OK;
+}
+
+// Enqueues the resolve on `st`: sub (or, when only the RGB8 is wanted, the staging sub), var, rgb.
+hipError_t accum_resolve_enqueue(rt_accum* a, double* d_sub, float* d_var, uint8_t* d_rgb, hipStream_t st) {
+    hipError_t e = rt::launch_accum_resolve(a->S, a->Q, (long)a->npix(), a->N, a->K, d_sub, d_var, st);
+    if (e == hipSuccess && d_rgb) {
+        rt::RenderArgs ra{};
+        ra.tw = a->width;
+        ra.th = a->height;
+        ra.rgb_out = d_rgb;
+        e = rt::launch_finalize_f64(ra, d_sub, st);
+    }
+    return e;
+}
+
+// rt_denoise_var*: denoise_run with the variance.
+int denoise_var_run(int32_t device, int32_t width, int32_t height, const double* d_sub, const float* d_feat,
+                    const float* d_var, int32_t levels, const float sigma[4], uint8_t* d_rgb, float* d_lin,
+                    float* d_vout, hipStream_t st) {
+    const long npix = (long)width * height;
+    hipError_t e = hipSuccess;
+    if (levels == 0) {
+        // the pass-through: rt_render's own RGB8 (k_finalize_f64), byte for byte
+        rt::RenderArgs a{};
+        a.tw = width;
+        a.th = height;
+        a.rgb_out = d_rgb;
+        e = rt::launch_finalize_f64(a, d_sub, st);
+        if (e == hipSuccess && !d_lin && !d_vout) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(RT_E_HIP, std::string("denoise_var: ") + hipGetErrorString(e));
+        if (!d_lin && !d_vout) return RT_OK;
+    }
+    const size_t bytes = rt::atrous_scratch_bytes(npix);
+    void* scratch = scratch_take(device, bytes, &e);
+    if (!scratch) return oom_or_hip(e, "denoise_var scratch");
+    e = rt::launch_atrous_var(width, height, d_sub, d_feat, d_var, levels, sigma[0], sigma[1], sigma[2], sigma[3],
+                              scratch, levels == 0 ? nullptr : d_rgb, d_lin, d_vout, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    scratch_give(device, scratch, bytes);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("denoise_var: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+}  // namespace
+
+int rt_accum_create(int32_t device, int32_t width, int32_t height, void** out) {
+    if (!out) return fail(RT_E_INVAL, "rt_accum_create: null argument");
+    *out = nullptr;
+    if (device < 0) return fail(RT_E_INVAL, "rt_accum_create: device ordinal must be >= 0");
+    if (width < 1 || height < 1) return fail(RT_E_INVAL, "rt_accum_create: width/height must be positive");
+    if ((int64_t)width * height > (int64_t)INT32_MAX) return fail(RT_E_INVAL, "rt_accum_create: image too large");
+    rt_accum* a = new rt_accum;
+    a->device = device;
+    a->width = width;
+    a->height = height;
+    *out = a;
+    return RT_OK;
+}
+
+void rt_accum_destroy(void* accum) {
+    rt_accum* a = (rt_accum*)accum;
+    if (!a) return;
+    if (a->S || a->stage) {
+        (void)hipSetDevice(a->device);
+        if (a->S) (void)hipFree(a->S);
+        if (a->stage) (void)hipFree(a->stage);
+    }
+    delete a;
+}
+
+int rt_accum_reset(void* accum) {
+    rt_accum* a = (rt_accum*)accum;
+    if (!a) return fail(RT_E_INVAL, "rt_accum_reset: null argument");
+    a->K = 0;  // the next pass stores without reading
+    a->N = 0;
+    return RT_OK;
+}
+
+int rt_accum_info(const void* accum, int64_t info[4]) {
+    const rt_accum* a = (const rt_accum*)accum;
+    if (!a || !info) return fail(RT_E_INVAL, "rt_accum_info: null argument");
+    info[0] = a->K;
+    info[1] = a->N;
+    info[2] = a->width;
+    info[3] = a->height;
+    return RT_OK;
+}
+
+int rt_accum_add(void* accum, const rt_scene* scene, const rt_render_params* p, const volatile int32_t* cancel,
+                 rt_render_stats* stats) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_accum_add(a, scene, p);
+    if (rc == RT_OK) rc = need_device("rt_accum_add", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc != RT_OK) return rc;
+    CallStream cs;  // destroyed last: after the stats' events and the cancel word have gone back
+    hipError_t ce = cs.init();
+    CancelMirror mirror;
+    if (ce == hipSuccess && cancel) ce = mirror.init();
+    if (ce != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_add: ") + hipGetErrorString(ce));
+    rt_render_stats local;
+    PendingStats ps;
+    ps.out = stats ? stats : &local;
+    hipStream_t st = cs.st;
+    rc = render_enqueue(const_cast<rt_scene*>(scene), p, a->stage_rgb(), a->stage_sub(), st, mirror.dev, cancel, &ps);
+    std::string err = g_err;
+    if (rc == RT_OK) {
+        // as rt_render: wait for the render while relaying the cancel flag
+        const hipError_t e = wait_stream(st, cancel, &mirror);
+        if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_accum_add: ") + hipGetErrorString(e); }
+        if (rc == RT_OK) {
+            const int f = ps.finish(&err);
+            if (f < 0) rc = f;
+        }
+        if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
+    } else {
+        (void)hipStreamSynchronize(st);
+    }
+    if (rc < 0) return fail(rc, err);
+    if (rc != RT_OK) return rc;  // cancelled: S, Q, K and N untouched
+    return accum_merge(a, a->stage_sub(), p->spp / 4, st);
+}
+
+int rt_accum_add_sub(void* accum, const double* sub, int32_t n) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_accum_sub("rt_accum_add_sub", a, sub, n);
+    if (rc == RT_OK) rc = need_device("rt_accum_add_sub", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc != RT_OK) return rc;
+    CallStream cs;
+    HIP_TRY(cs.init());
+    HIP_TRY(hipMemcpyAsync(a->stage_sub(), sub, a->sub_bytes(), hipMemcpyHostToDevice, cs.st));
+    return accum_merge(a, a->stage_sub(), n, cs.st);
+}
+
+int rt_accum_add_sub_device(void* accum, const void* d_sub, int32_t n, void* stream) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_accum_sub("rt_accum_add_sub_device", a, d_sub, n);
+    if (rc == RT_OK) rc = need_device("rt_accum_add_sub_device", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, false);
+    if (rc != RT_OK) return rc;
+    return accum_merge(a, (const double*)d_sub, n, (hipStream_t)stream);
+}
+
+int rt_accum_resolve_device(void* accum, void* d_sub, void* d_var, void* d_rgb, void* stream) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_accum_resolve("rt_accum_resolve_device", a, d_var);
+    if (rc == RT_OK) rc = need_device("rt_accum_resolve_device", a->device);
+    const bool stage = d_rgb && !d_sub;
+    if (rc == RT_OK) rc = accum_ready(a, true, stage);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = accum_resolve_enqueue(a, stage ? a->stage_sub() : (double*)d_sub, (float*)d_var, (uint8_t*)d_rgb, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_resolve_device: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_accum_resolve(void* accum, double* sub_out, float* var_out, uint8_t* rgb_out) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_accum_resolve("rt_accum_resolve", a, var_out);
+    if (rc == RT_OK) rc = need_device("rt_accum_resolve", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc != RT_OK) return rc;
+    CallStream cs;
+    HIP_TRY(cs.init());
+    hipStream_t st = cs.st;
+    const bool want_sub = sub_out || rgb_out;
+    hipError_t e = accum_resolve_enqueue(a, want_sub ? a->stage_sub() : nullptr, var_out ? a->stage_var() : nullptr,
+                                         rgb_out ? a->stage_rgb() : nullptr, st);
+    if (e == hipSuccess && sub_out) e = hipMemcpyAsync(sub_out, a->stage_sub(), a->sub_bytes(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && var_out)
+        e = hipMemcpyAsync(var_out, a->stage_var(), a->npix() * 4 * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && rgb_out) e = hipMemcpyAsync(rgb_out, a->stage_rgb(), a->npix() * 3, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_resolve: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_denoise_var_device(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
+                          const float* var, int32_t levels, float sigma_c, float sigma_n, float sigma_z,
+                          float sigma_a, uint8_t* rgb_out, float* lin_out, float* var_out, void* stream) {
+    const float sigma[4] = {sigma_c, sigma_n, sigma_z, sigma_a};
+    if (!var) return fail(RT_E_INVAL, "rt_denoise_var_device: null argument");
+    int rc = check_denoise("rt_denoise_var_device", width, height, sub, feat, levels, sigma, rgb_out);
+    if (rc == RT_OK) rc = need_device("rt_denoise_var_device", device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    return denoise_var_run(device, width, height, sub, feat, var, levels, sigma, rgb_out, lin_out, var_out,
+                           (hipStream_t)stream);
+}
+
+int rt_denoise_var(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
+                   const float* var, int32_t levels, float sigma_c, float sigma_n, float sigma_z, float sigma_a,
+                   uint8_t* rgb_out, float* lin_out, float* var_out) {
+    const float sigma[4] = {sigma_c, sigma_n, sigma_z, sigma_a};
+    if (!var) return fail(RT_E_INVAL, "rt_denoise_var: null argument");
+    int rc = check_denoise("rt_denoise_var", width, height, sub, feat, levels, sigma, rgb_out);
+    if (rc == RT_OK) rc = need_device("rt_denoise_var", device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t npix = (size_t)width * height;
+    const size_t b_sub = npix * 12 * sizeof(double), b_feat = npix * rt::kFeatFloats * sizeof(float);
+    const size_t b_var = npix * 4 * sizeof(float), b_lin = align_up(npix * 3 * sizeof(float), 16);
+    const size_t b_vout = align_up(npix * sizeof(float), 16), b_rgb = align_up(npix * 3, 16);
+    // one allocation: sub | feat | var | lin | vout | rgb (each part 16-byte aligned)
+    char* buf = nullptr;
+    hipError_t e = hipMalloc((void**)&buf, b_sub + b_feat + b_var + b_lin + b_vout + b_rgb);
+    if (e != hipSuccess) return oom_or_hip(e, "rt_denoise_var buffers");
+    double* d_sub = (double*)buf;
+    float* d_feat = (float*)(buf + b_sub);
+    float* d_var = (float*)(buf + b_sub + b_feat);
+    float* d_lin = (float*)(buf + b_sub + b_feat + b_var);
+    float* d_vout = (float*)(buf + b_sub + b_feat + b_var + b_lin);
+    uint8_t* d_rgb = (uint8_t*)(buf + b_sub + b_feat + b_var + b_lin + b_vout);
+    hipStream_t st = nullptr;
+    e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_sub, sub, b_sub, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_feat, feat, b_feat, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_var, var, b_var, hipMemcpyHostToDevice, st);
+    std::string err;
+    if (e == hipSuccess) {
+        rc = denoise_var_run(device, width, height, d_sub, d_feat, d_var, levels, sigma, d_rgb, lin_out ? d_lin : nullptr,
+                             var_out ? d_vout : nullptr, st);
+        err = g_err;
+    }
+    if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync(rgb_out, d_rgb, npix * 3, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && rc == RT_OK && lin_out)
+        e = hipMemcpyAsync(lin_out, d_lin, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && rc == RT_OK && var_out)
+        e = hipMemcpyAsync(var_out, d_vout, npix * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (st) {
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = es;
+        (void)hipStreamDestroy(st);
+    }
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_denoise_var: ") + hipGetErrorString(e));
     return rc < 0 ? fail(rc, err) : rc;
 }
 

@@ -7,7 +7,8 @@ Reference interface it mirrors (SuneelFreimuth/raytracer-server):
                                               (same 6-byte header + RGB8 chunk messages)
   Scene.trace_ray(origins, dirs)           <- Scene::trace_ray            src/scene.rs:272-289
 Beyond the reference: render_features / denoise / render_denoised, denoised previews at low spp
-(rt_render_features, rt_denoise).
+(rt_render_features, rt_denoise). Accumulator / denoise_var / render_progressive: progressive refinement
+(rt_accum_*, rt_denoise_var).
 
 Everything computes on the GPU through lib/librtamd.so; there is no CPU fallback. Importing this
 module without the built library raises ImportError.
@@ -75,7 +76,10 @@ class SceneDesc(ctypes.Structure):
 
 _EXPORTS = ["rt_scene_load_toml", "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh",
             "rt_render", "rt_render_device", "rt_render_multi", "rt_band_plan", "rt_trace_rays", "rt_trace_rays_flags", "rt_last_error", "rt_abi_version",
-            "rt_device_count", "rt_render_features", "rt_render_features_device", "rt_denoise", "rt_denoise_device"]
+            "rt_device_count", "rt_render_features", "rt_render_features_device", "rt_denoise", "rt_denoise_device",
+            "rt_accum_create", "rt_accum_destroy", "rt_accum_reset", "rt_accum_info", "rt_accum_add", "rt_accum_add_sub",
+            "rt_accum_add_sub_device", "rt_accum_resolve", "rt_accum_resolve_device", "rt_denoise_var",
+            "rt_denoise_var_device"]
 
 
 def _load():
@@ -110,6 +114,18 @@ def _load():
     L.rt_render_features_device.argtypes = [vp, P(RenderParams), vp, vp]
     L.rt_denoise.argtypes = [I, I, I, P(ctypes.c_double), P(F), I, F, F, F, F, P(ctypes.c_uint8), P(F)]
     L.rt_denoise_device.argtypes = [I, I, I, vp, vp, I, F, F, F, F, vp, vp, vp]
+    L.rt_accum_create.argtypes = [I, I, I, P(vp)]
+    L.rt_accum_destroy.argtypes = [vp]
+    L.rt_accum_destroy.restype = None
+    L.rt_accum_reset.argtypes = [vp]
+    L.rt_accum_info.argtypes = [vp, P(ctypes.c_int64)]
+    L.rt_accum_add.argtypes = [vp, vp, P(RenderParams), P(ctypes.c_int32), P(RenderStats)]
+    L.rt_accum_add_sub.argtypes = [vp, P(ctypes.c_double), I]
+    L.rt_accum_add_sub_device.argtypes = [vp, vp, I, vp]
+    L.rt_accum_resolve.argtypes = [vp, P(ctypes.c_double), P(F), P(ctypes.c_uint8)]
+    L.rt_accum_resolve_device.argtypes = [vp, vp, vp, vp, vp]
+    L.rt_denoise_var.argtypes = [I, I, I, P(ctypes.c_double), P(F), P(F), I, F, F, F, F, P(ctypes.c_uint8), P(F), P(F)]
+    L.rt_denoise_var_device.argtypes = [I, I, I, vp, vp, vp, I, F, F, F, F, vp, vp, vp, vp]
     L.rt_last_error.restype = ctypes.c_char_p
     L.rt_last_error.argtypes = []
     L.rt_abi_version.argtypes = []
@@ -394,6 +410,154 @@ def render_denoised(scene, width, height, spp, seed=0x5EED, device=0, cancel=Non
         return None
     feat = render_features(scene, width, height, mesh_nearest=mesh_nearest, device=device)
     return denoise(sub, feat, want_linear=want_linear, device=device, **denoise_params)
+
+
+# Progressive accumulation -------------------------------------------------------------------
+
+# Defaults of denoise_var / render_progressive (the C ABI has none). Chosen on a grid by the linear RMSE of the
+# filtered accumulated frame against a 4096-spp frame of another seed, at 16, 64 and 1024 spp on the three scenes
+# (tools/denoise_probe.py --var-grid).
+DENOISE_VAR_DEFAULTS = dict(levels=3, sigma_c=4.0, sigma_n=0.3, sigma_z=0.05, sigma_a=0.3)
+
+PASS_SEED_STEP = 0x9E3779B97F4A7C15  # render_progressive: pass k renders with seed + k * PASS_SEED_STEP (mod 2^64)
+
+
+class Accumulator:
+    """rt_accum: merges render passes of one width x height frame on one device and estimates each pixel's variance
+    from the pass-to-pass scatter. Not thread-safe. The device memory (192 bytes per pixel, plus 115 of staging) comes
+    with the first pass."""
+
+    def __init__(self, width, height, device=0):
+        h = ctypes.c_void_p()
+        _check(lib.rt_accum_create(device, width, height, ctypes.byref(h)))
+        self._h = h
+        self.width, self.height, self.device = width, height, device
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            lib.rt_accum_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    def reset(self):
+        _check(lib.rt_accum_reset(self._h))
+
+    def info(self):
+        a = np.zeros(4, dtype=np.int64)
+        _check(lib.rt_accum_info(self._h, _ptr(a, ctypes.c_int64)))
+        return dict(passes=int(a[0]), n=int(a[1]), width=int(a[2]), height=int(a[3]))
+
+    def add(self, scene, spp, seed, mis=False, megakernel=True, mesh_nearest=False, fp32=False, cancel=None):
+        """Renders the whole frame at `spp` with `seed` (rt_accum_add) and merges it with n = spp // 4. Returns the
+        render's stats; stats["cancelled"] is True when the cancel word stopped the pass (nothing was merged)."""
+        flags = (FLAG_MIS if mis else 0) | (FLAG_MEGAKERNEL if megakernel else 0) | \
+            (FLAG_MESH_NEAREST if mesh_nearest else 0) | (FLAG_FP32 if fp32 else 0)
+        p = make_params(self.width, self.height, spp, seed, None, flags, self.device, 1)
+        st = RenderStats()
+        rc = _check(lib.rt_accum_add(self._h, scene.handle, ctypes.byref(p),
+                                     ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st)))
+        out = st.as_dict()
+        out["cancelled"] = rc == RT_CANCELLED
+        return out
+
+    def add_sub(self, sub, n):
+        """Merges a pass rendered elsewhere: sub[h, w, 4, 3] f64 (render's want_sub output), n = its spp // 4."""
+        sub = np.ascontiguousarray(sub, dtype=np.float64)
+        if sub.shape != (self.height, self.width, 4, 3):
+            raise ValueError(f"Accumulator.add_sub: sub {sub.shape} is not [{self.height}, {self.width}, 4, 3]")
+        _check(lib.rt_accum_add_sub(self._h, _ptr(sub, ctypes.c_double), n))
+
+    def resolve(self, want_sub=True, want_var=False, want_rgb=True):
+        """The accumulated frame: (sub[h, w, 4, 3] f64, var[h, w, 4] f32, rgb[h, w, 3] u8), None for what was not
+        asked for. var (the variance of the clamped pixel colour: r, g, b and their sum) needs two passes."""
+        h, w = self.height, self.width
+        sub = np.zeros((h, w, 4, 3), dtype=np.float64) if want_sub else None
+        var = np.zeros((h, w, 4), dtype=np.float32) if want_var else None
+        rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+        _check(lib.rt_accum_resolve(self._h, _ptr(sub, ctypes.c_double), _ptr(var, ctypes.c_float),
+                                    _ptr(rgb, ctypes.c_uint8)))
+        return sub, var, rgb
+
+
+def denoise_var(sub, feat, var, levels=None, sigma_c=None, sigma_n=None, sigma_z=None, sigma_a=None,
+                want_linear=False, want_var=False, device=0):
+    """Variance-guided a-trous filter (rt_denoise_var): denoise with the colour term scaled by var[h, w, 4]
+    (Accumulator.resolve's; only [..., 3] is used). Parameters left None come from DENOISE_VAR_DEFAULTS. Returns
+    rgb[h, w, 3] u8, followed by the linear float32[h, w, 3] with want_linear and the filtered variance
+    float32[h, w] with want_var."""
+    d = DENOISE_VAR_DEFAULTS
+    levels = d["levels"] if levels is None else levels
+    sig = [d[k] if v is None else v for k, v in (("sigma_c", sigma_c), ("sigma_n", sigma_n), ("sigma_z", sigma_z),
+                                                 ("sigma_a", sigma_a))]
+    sub = np.ascontiguousarray(sub, dtype=np.float64)
+    feat = np.ascontiguousarray(feat, dtype=np.float32)
+    var = np.ascontiguousarray(var, dtype=np.float32)
+    h, w = sub.shape[:2]
+    if sub.shape != (h, w, 4, 3) or feat.shape != (h, w, 8) or var.shape != (h, w, 4):
+        raise ValueError(f"denoise_var: sub {sub.shape} / feat {feat.shape} / var {var.shape} are not [h, w, 4, 3] / "
+                         "[h, w, 8] / [h, w, 4]")
+    rgb = np.zeros((h, w, 3), dtype=np.uint8)
+    lin = np.zeros((h, w, 3), dtype=np.float32) if want_linear else None
+    vout = np.zeros((h, w), dtype=np.float32) if want_var else None
+    F = ctypes.c_float
+    _check(lib.rt_denoise_var(device, w, h, _ptr(sub, ctypes.c_double), _ptr(feat, F), _ptr(var, F), levels, *sig,
+                              _ptr(rgb, ctypes.c_uint8), _ptr(lin, F), _ptr(vout, F)))
+    out = (rgb,) + ((lin,) if want_linear else ()) + ((vout,) if want_var else ())
+    return out if len(out) > 1 else rgb
+
+
+def progressive_passes(spp, first=8):
+    """The pass sizes of render_progressive: first/2, first/2, then each pass as large as the total so far, the last
+    cut to reach 4 * floor(spp / 4). Every pass is a multiple of 4 (first/2 is rounded down to one, at least 4)."""
+    total = 4 * (spp // 4)
+    if total < 4:
+        raise ValueError("progressive_passes: spp must be >= 4")
+    half = max(4, first // 2 // 4 * 4)
+    sizes, done = [], 0
+    while done < total:
+        size = min(half if len(sizes) < 2 else done, total - done)
+        sizes.append(size)
+        done += size
+    return sizes
+
+
+def render_progressive(scene, width, height, spp, first=8, seed=0x5EED, device=0, cancel=None, **denoise_params):
+    """A generator that refines a frame pass by pass and yields (rgb[h, w, 3] u8, spp so far). Passes:
+    progressive_passes(spp, first); pass k renders with seed + k * PASS_SEED_STEP (mod 2^64) on the megakernel and is
+    merged into an Accumulator. After every pass from the second on: resolve, render_features (once), denoise_var
+    (denoise_params: levels / sigma_*, DENOISE_VAR_DEFAULTS otherwise). A frame of one pass only (spp < 8) is yielded
+    unfiltered. A raised cancel word ends the generator."""
+    sizes = progressive_passes(spp, first)
+    feat, done = None, 0
+    with Accumulator(width, height, device) as acc:
+        for k, size in enumerate(sizes):
+            st = acc.add(scene, size, (seed + k * PASS_SEED_STEP) % (1 << 64), cancel=cancel)
+            if st["cancelled"]:
+                return
+            done += size
+            if k == 0:
+                if len(sizes) == 1:
+                    yield acc.resolve(want_sub=False)[2], done
+                continue
+            sub, var, _ = acc.resolve(want_var=True, want_rgb=False)
+            if feat is None:
+                feat = render_features(scene, width, height, device=device)
+            yield denoise_var(sub, feat, var, device=device, **denoise_params), done
 
 
 def band_plan(tile_h, n_workers, band_rows=0):

@@ -13,6 +13,8 @@ reference's panics (bad JSON, unknown scene) become logged errors.
 
 Run:  PORT=8080 python -m rt_amd.server <scenes dir>
       RT_DENOISE=<levels> selects denoised previews (whole frames through rt_amd.render_denoised).
+      RT_PROGRESSIVE=<first_spp> selects progressive jobs (whole frames through rt_amd.render_progressive, each refined
+      frame re-sent with the same chunk messages).
 """
 import asyncio
 import ctypes
@@ -104,15 +106,65 @@ class RenderJob:
         return False
 
 
+class ProgressiveJob:
+    """A whole-frame job that refines its frame pass by pass (rt_amd.render_progressive): every
+    refined frame is sent again with the same chunk messages (they carry x and y, so a client simply overwrites).
+    RenderJob's interface: a stop takes effect between passes, and inside a pass through the cancel word."""
+
+    def __init__(self, send, first=8, device=0, **denoise_params):
+        self.send = send
+        self.first = first
+        self.device = device
+        self.denoise_params = denoise_params
+        self.cancel = ctypes.c_int32(1)  # starts cancelled == not running
+
+    def running(self):
+        return self.cancel.value == 0
+
+    def stop(self):
+        self.cancel.value = 1
+
+    async def run(self, scene, width, height, spp, seed):
+        """Returns True when stopped before the last frame was sent."""
+        import rt_amd
+
+        self.cancel.value = 0
+        loop = asyncio.get_running_loop()
+        frames = rt_amd.render_progressive(scene, width, height, spp, first=self.first, seed=seed, device=self.device,
+                                           cancel=self.cancel, **self.denoise_params)
+        total = 4 * (spp // 4)
+        try:
+            while True:
+                if self.cancel.value:
+                    return True
+                frame = await loop.run_in_executor(None, next, frames, None)
+                if frame is None or self.cancel.value:
+                    return True
+                rgb, done = frame
+                for msg in chunk_messages(rgb, 0):
+                    try:
+                        await self.send(msg)
+                    except ConnectionError:
+                        self.cancel.value = 1
+                        return True
+                if done >= total:
+                    self.cancel.value = 1
+                    return False
+        finally:
+            frames.close()
+
+
 class Server:
-    def __init__(self, scenes, renderer=None, width=WIDTH, height=HEIGHT, band_rows=32, log=print):
+    def __init__(self, scenes, renderer=None, width=WIDTH, height=HEIGHT, band_rows=32, log=print, job_factory=None):
         self.scenes = scenes
-        self.renderer = renderer or gpu_band_renderer()
+        self.renderer = renderer or (gpu_band_renderer() if job_factory is None else None)
         self.width = width
         self.height = height
         self.band_rows = band_rows
         self.connections = set()
         self.log = log
+        # job_factory(send) makes a connection's job (RenderJob's interface); None: RenderJob over `renderer`
+        self.job_factory = job_factory
 
     def new_id(self):  # server.rs:63-78
         while True:
@@ -128,7 +180,8 @@ class Server:
         await ws.prepare(request)
         cid = self.new_id()
         self.log(f"[{cid}] Accepted connection.")
-        job = RenderJob(ws.send_bytes, self.renderer, self.band_rows)
+        job = self.job_factory(ws.send_bytes) if self.job_factory else RenderJob(ws.send_bytes, self.renderer,
+                                                                                 self.band_rows)
         task = None
         try:
             async for msg in ws:
@@ -193,7 +246,13 @@ def main(argv=None):
         # (geometry.rs:886-903), not the reference's first-hit octree walk (geometry.rs:1237-1295)
         print("RT_PRECISION=f32: f32 perf mode; meshes (flying_unicorn) use nearest-triangle hits, not the "
               "reference's octree semantics; frames differ statistically from server.rs", file=sys.stderr)
-    if "RT_DENOISE" in os.environ:
+    if "RT_PROGRESSIVE" in os.environ:
+        # progressive refinement: whole frames, each refined frame re-sent with the same chunk messages
+        first = int(os.environ["RT_PROGRESSIVE"])
+        print(f"RT_PROGRESSIVE={first}: whole-frame progressive jobs, first frame at {first} spp, variance-guided "
+              "a-trous filter", file=sys.stderr)
+        server = Server(scenes, job_factory=lambda send: ProgressiveJob(send, first=first))
+    elif "RT_DENOISE" in os.environ:
         # denoised previews: whole frames (the filter needs an apron of 2 * (2^levels - 1) rows around a band)
         levels = int(os.environ["RT_DENOISE"])
         print(f"RT_DENOISE={levels}: whole-frame renders, {levels}-level a-trous filter", file=sys.stderr)
