@@ -238,6 +238,42 @@ extern "C" {
         var_out: *mut f32, stream: *mut c_void,
     ) -> c_int;
 
+    /// Rendering to a per-pixel error target (rt_ffi.h). Renders only the listed pixels of the
+    /// whole frame `params`: `pixels` are `n_pixels` strictly ascending ids `row * width + col`; entry `e` of
+    /// `rgb_out` (n * 3, nullable) and `sub_out` (n * 12, nullable) is `rt_render`'s output of that pixel.
+    pub fn rt_render_pixels(
+        scene: *const RtScene, params: *const RtRenderParams, pixels: *const u32, n_pixels: i64, rgb_out: *mut u8,
+        sub_out: *mut f64, cancel: *const i32, stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// The same with device buffers, enqueued on `stream`; the list is the caller's contract.
+    pub fn rt_render_pixels_device(
+        scene: *const RtScene, params: *const RtRenderParams, d_pixels: *const c_void, n_pixels: i64,
+        d_rgb: *mut c_void, d_sub: *mut c_void, stream: *mut c_void, stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// Renders the listed pixels and merges them (needs two full-frame passes first); `RT_CANCELLED` merges nothing.
+    pub fn rt_accum_add_pixels(
+        accum: *mut c_void, scene: *const RtScene, params: *const RtRenderParams, pixels: *const u32, n_pixels: i64,
+        cancel: *const i32, stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// Merges a compact pass: `sub` n_pixels * 12 f64 (host), `n` >= 1 samples per subpixel.
+    pub fn rt_accum_add_sub_pixels(
+        accum: *mut c_void, pixels: *const u32, n_pixels: i64, sub: *const f64, n: i32,
+    ) -> c_int;
+    pub fn rt_accum_add_sub_pixels_device(
+        accum: *mut c_void, d_pixels: *const c_void, n_pixels: i64, d_sub: *const c_void, n: i32, stream: *mut c_void,
+    ) -> c_int;
+    /// The per-pixel passes and samples per subpixel (width * height u32 each, either nullable).
+    pub fn rt_accum_counts(accum: *mut c_void, k_out: *mut u32, n_out: *mut u32) -> c_int;
+    /// The pixels whose estimated error is above the target, ascending; at most `cap` are written, `n_out` is the
+    /// full count. `max_n` > 0 excludes pixels that already hold that many samples per subpixel.
+    pub fn rt_accum_select(
+        accum: *mut c_void, abs_tol: f32, rel_tol: f32, max_n: i32, pixels_out: *mut u32, cap: i64, n_out: *mut i64,
+    ) -> c_int;
+    pub fn rt_accum_select_device(
+        accum: *mut c_void, abs_tol: f32, rel_tol: f32, max_n: i32, d_pixels: *mut c_void, cap: i64, n_out: *mut i64,
+        stream: *mut c_void,
+    ) -> c_int;
+
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_abi_version() -> c_int;
     pub fn rt_device_count() -> c_int;

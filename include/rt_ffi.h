@@ -16,6 +16,8 @@
  *   rt_render_features, rt_denoise: no counterpart in the reference (denoised previews at low spp)
  *   rt_accum_*, rt_denoise_var: no counterpart either (progressive refinement: merged passes, their variance, and
  *                          a filter guided by it)
+ *   rt_render_pixels, rt_accum_select, rt_accum_add_pixels: no counterpart either (rendering to a per-pixel error
+ *                          target with sparse pixel-list passes)
  *
  * Conventions (mirroring the reference's):
  *   - a scene is immutable after creation and may be shared by concurrent rt_render calls
@@ -42,7 +44,9 @@ extern "C" {
 
 #define RT_ABI_VERSION 3  /* 2: rt_render_params.row_step; 3: rt_render_multi. The denoised-preview entry points
                              (rt_render_features*, rt_denoise*) are additive: no struct or existing call changed, so
-                             the version stays 3; likewise progressive accumulation (rt_accum_*, rt_denoise_var*) */
+                             the version stays 3; likewise progressive accumulation (rt_accum_*, rt_denoise_var*) and
+                             the error-target calls (rt_render_pixels*, rt_accum_add_pixels, rt_accum_add_sub_pixels*,
+                             rt_accum_counts, rt_accum_select*) */
 
 /* return codes */
 #define RT_OK 0
@@ -273,6 +277,64 @@ int rt_denoise_var(int32_t device, int32_t width, int32_t height, const double* 
 int rt_denoise_var_device(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
                           const float* var, int32_t levels, float sigma_c, float sigma_n, float sigma_z,
                           float sigma_a, uint8_t* rgb_out, float* lin_out, float* var_out, void* stream);
+
+/* Rendering to a per-pixel error target ------------------------------------------- */
+/* Renders only the listed pixels of the frame of `params`. pixels: n_pixels frame pixel ids, id = row * width + col
+ * (row 0 = top), strictly ascending, each < width * height. params must be the whole frame, as rt_accum_add requires
+ * it: x0 = y0 = 0, tile_w = width, tile_h = height, row_step 0 or 1. Entry e of the outputs is pixel pixels[e]:
+ * sub_out[e] (12 f64) is rt_render's sub_out of that pixel for the same seed, spp and flags, bit for bit, and
+ * rgb_out[e] its RGB8, byte for byte. The f64 fused megakernel's per-vertex code runs it (k_render_list_f64):
+ * RT_FLAG_MIS passes through, RT_FLAG_MEGAKERNEL is implied; RT_FLAG_FP32 and RT_FLAG_MESH_NEAREST are out of scope
+ * (RT_E_INVAL). n_pixels * 4 must fit an int32. The host form checks the list (RT_E_INVAL before any device call);
+ * n_pixels = 0 returns RT_OK without a launch and leaves the outputs untouched. cancel and stats as in rt_render;
+ * stats->samples = n_pixels * 4 * floor(spp / 4). Every argument check runs without a GPU. */
+int rt_render_pixels(const rt_scene* scene, const rt_render_params* params, const uint32_t* pixels, int64_t n_pixels,
+                     uint8_t* rgb_out /* n * 3, may be NULL */, double* sub_out /* n * 12, may be NULL */,
+                     const volatile int32_t* cancel, rt_render_stats* stats);
+/* The same with device buffers on params->device (d_pixels 4-byte, d_sub 16-byte aligned; d_rgb, d_sub nullable),
+ * enqueued on `stream`; synchronous with respect to the stream only when stats != NULL. A strictly ascending
+ * in-range list is the caller's contract here: it is not checked. */
+int rt_render_pixels_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
+                            int64_t n_pixels, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats);
+
+/* Sparse passes into an accumulator. The first sparse merge gives the accumulator per-pixel counts (K_p, N_p), 8 bytes
+ * per pixel (allocated together with a pixel-list buffer and the selection's scratch, about 12.2 bytes per pixel in
+ * all, by the first sparse merge or selection), filled with the frame's (K, N) at that moment; from then on a full-frame merge adds (1, n) to every
+ * pixel, a sparse merge to the listed ones, and rt_accum_resolve uses N_p and K_p - 1 where it used N and K - 1. An
+ * accumulator that never receives a sparse pass computes exactly what it did before. A sparse merge needs K >= 2
+ * full-frame passes first (RT_E_INVAL otherwise), so every K_p >= 2. rt_accum_info keeps reporting the full-frame
+ * passes' K and N only; rt_accum_reset forgets the per-pixel counts too.
+ * rt_accum_add_pixels renders the listed pixels (rt_render_pixels' rules for params, flags and the list; spp >= 4 and
+ * params->device the accumulator's) into the staging buffer and merges them with n = floor(spp / 4); a cancelled pass
+ * returns RT_CANCELLED and merges nothing. */
+int rt_accum_add_pixels(void* accum, const rt_scene* scene, const rt_render_params* params, const uint32_t* pixels,
+                        int64_t n_pixels, const volatile int32_t* cancel, rt_render_stats* stats);
+/* Merges a compact pass rendered elsewhere: sub[e] (12 f64, host) belongs to pixel pixels[e] (host; strictly
+ * ascending, each < width * height, checked), n >= 1 its samples per subpixel. n_pixels = 0 merges nothing. */
+int rt_accum_add_sub_pixels(void* accum, const uint32_t* pixels, int64_t n_pixels, const double* sub, int32_t n);
+/* The same from device buffers of the accumulator's device (d_sub 16-byte aligned), enqueued on `stream`; the list
+ * is the caller's contract (unique ids in range). */
+int rt_accum_add_sub_pixels_device(void* accum, const void* d_pixels, int64_t n_pixels, const void* d_sub, int32_t n,
+                                   void* stream);
+/* The per-pixel maps K_p and N_p (width * height uint32 each, host, either may be NULL); the frame's K and N
+ * everywhere while no sparse pass has been merged (then without a device call). */
+int rt_accum_counts(void* accum, uint32_t* k_out, uint32_t* n_out);
+/* The pixels whose estimated error is still above a target (K >= 2; tolerances >= 0 and not NaN; RT_E_INVAL
+ * otherwise). Arithmetic, fixed in f64 without FMA contraction so that numpy gives the same bits: with var the
+ * resolve's var_out and m = S / N_p,
+ *   g_p = sum k[dx] k[dy] (double)var[q][3] / sum k[dx] k[dy],   q = p + (dx, dy), dx, dy in -1..1, inside the image,
+ *         row-major (dy, dx) order, k = (1/4, 1/2, 1/4) (the tent of rt_denoise_var)
+ *   c   = sum_j clamp(m_j, 0, 1) * 0.25 in j order,   y = (c_r + c_g) + c_b
+ *   thr = ((double)rel_tol * y) / 3.0 + (double)abs_tol
+ * pixel p is active iff g_p > thr * thr and (max_n <= 0 or N_p < max_n). pixels_out receives the active ids in
+ * ascending order, at most cap of them (cap >= 0; pixels_out may be NULL when cap = 0); *n_out is always the full
+ * count. */
+int rt_accum_select(void* accum, float abs_tol, float rel_tol, int32_t max_n, uint32_t* pixels_out, int64_t cap,
+                    int64_t* n_out);
+/* The same into a device buffer of the accumulator's device, enqueued on `stream`; the call waits for the selection
+ * and then writes *n_out on the host. */
+int rt_accum_select_device(void* accum, float abs_tol, float rel_tol, int32_t max_n, void* d_pixels, int64_t cap,
+                           int64_t* n_out, void* stream);
 
 const char* rt_last_error(void);
 int rt_abi_version(void);

@@ -14,4 +14,23 @@ hipError_t launch_accum_add(double* S, double* Q, const double* m, long npix, in
 hipError_t launch_accum_resolve(const double* S, const double* Q, long npix, int64_t N, int64_t K, double* sub,
                                 float* var, hipStream_t st);
 
+// Per-pixel counts and sparse merges. cnt[pix][2] = (K_p, N_p): the passes and samples per subpixel
+// merged into pixel p.
+// cnt[p] = (K, N) for every pixel (add false), or cnt[p] += (K, N) (add true: a full-frame merge of K passes).
+hipError_t launch_accum_cnt_fill(uint32_t* cnt, long npix, uint32_t K, uint32_t N, bool add, hipStream_t st);
+// The pass m[e][4][3] of the n_list unique pixels list[e] (ids < npix): S[p] += n m, Q[p] += (n m) m with
+// launch_accum_add's expression, cnt[p] += (1, n). m 16-byte aligned.
+hipError_t launch_accum_add_list(double* S, double* Q, uint32_t* cnt, const uint32_t* list, long n_list, const double* m,
+                                 int32_t n, hipStream_t st);
+// launch_accum_resolve with N_p and K_p - 1 of cnt (every K_p >= 2 when var is wanted).
+hipError_t launch_accum_resolve_cnt(const double* S, const double* Q, const uint32_t* cnt, long npix, double* sub,
+                                    float* var, hipStream_t st);
+// Selection (rt_ffi.h rt_accum_select): the ids of the active pixels, ascending, by a two-pass compaction. var: the
+// resolve's float[pix][4]; cnt: per-pixel counts or null (then every N_p = N); scratch: select_scratch_bytes(npix)
+// bytes, 8-byte aligned. At most cap ids go to out; *total (device) is the full count.
+size_t select_scratch_bytes(long npix);
+hipError_t launch_accum_select(const double* S, const float* var, const uint32_t* cnt, int64_t N, int width, int height,
+                               float abs_tol, float rel_tol, int32_t max_n, void* scratch, uint32_t* out, long cap,
+                               uint32_t* total, hipStream_t st);
+
 }  // namespace rt

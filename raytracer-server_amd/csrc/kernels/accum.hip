@@ -4,6 +4,9 @@
 //   k_accum_resolve — the accumulated subpixel means S / N and the variance of the clamped pixel colour.
 // Both stream: every access is a 16-byte load or store of consecutive lanes. Compiled without FMA contraction (the
 // Makefile's -ffp-contract=off), so tests/accum_ref.py restates them bit for bit.
+// Rendering to an error target (restated by tests/adapt_ref.py):
+//   k_accum_cnt_fill, k_accum_add_list, k_accum_resolve_cnt — per-pixel counts (K_p, N_p) and sparse merges.
+//   k_select_count / k_select_scan / k_select_write — the pixels whose estimated error is above a target, ascending.
 #include <hip/hip_runtime.h>
 
 #include "accum.h"
@@ -28,12 +31,10 @@ __global__ __launch_bounds__(256) void k_accum_add(double2* __restrict__ S, doub
     Q[i] = q;
 }
 
-// One lane per pixel. K1 = K - 1 (unused when var is null).
-__global__ __launch_bounds__(256) void k_accum_resolve(const double2* __restrict__ S, const double2* __restrict__ Q,
-                                                       long npix, double N, double K1, double2* __restrict__ sub,
-                                                       float4* __restrict__ var) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
+// Pixel p's resolve with N samples per subpixel and K1 = K - 1 (unused when var is null).
+__device__ __forceinline__ void resolve_pixel(const double2* __restrict__ S, const double2* __restrict__ Q, long p,
+                                              double N, double K1, double2* __restrict__ sub,
+                                              float4* __restrict__ var) {
     double m[12];
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
@@ -69,6 +70,220 @@ __global__ __launch_bounds__(256) void k_accum_resolve(const double2* __restrict
     }
 }
 
+// One lane per pixel, one K and N for the frame.
+__global__ __launch_bounds__(256) void k_accum_resolve(const double2* __restrict__ S, const double2* __restrict__ Q,
+                                                       long npix, double N, double K1, double2* __restrict__ sub,
+                                                       float4* __restrict__ var) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    resolve_pixel(S, Q, p, N, K1, sub, var);
+}
+
+// The same with the pixel's own counts: N_p and K_p - 1.
+__global__ __launch_bounds__(256) void k_accum_resolve_cnt(const double2* __restrict__ S, const double2* __restrict__ Q,
+                                                           const uint2* __restrict__ cnt, long npix,
+                                                           double2* __restrict__ sub, float4* __restrict__ var) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const uint2 c = cnt[p];
+    resolve_pixel(S, Q, p, (double)c.y, (double)c.x - 1.0, sub, var);
+}
+
+// Per-pixel counts and sparse merges ---------------------------------------------------------
+
+// cnt[p] = (K, N), or cnt[p] += (K, N). One lane per pixel.
+template <bool kAdd>
+__global__ __launch_bounds__(256) void k_accum_cnt_fill(uint2* __restrict__ cnt, long npix, uint32_t K, uint32_t N) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    uint2 c = make_uint2(K, N);
+    if (kAdd) {
+        const uint2 c0 = cnt[p];
+        c = make_uint2(c0.x + K, c0.y + N);
+    }
+    cnt[p] = c;
+}
+
+// One lane per (list entry, pair of elements): k_accum_add<false>'s expression at the entry's pixel. The list is
+// unique, so no two lanes touch one element; the lane of pair 0 counts the pass.
+__global__ __launch_bounds__(256) void k_accum_add_list(double2* __restrict__ S, double2* __restrict__ Q,
+                                                        uint2* __restrict__ cnt, const uint32_t* __restrict__ list,
+                                                        const double2* __restrict__ m, long npairs, double n,
+                                                        uint32_t n_u) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npairs) return;
+    const long e = i / 6;
+    const int k = (int)(i - e * 6);
+    const uint32_t p = list[e];
+    const size_t at = (size_t)p * 6 + k;
+    const double2 v = m[i];
+    const double ax = n * v.x, ay = n * v.y;
+    const double2 s0 = S[at], q0 = Q[at];
+    S[at] = make_double2(s0.x + ax, s0.y + ay);
+    Q[at] = make_double2(q0.x + ax * v.x, q0.y + ay * v.y);
+    if (k == 0) {
+        const uint2 c = cnt[p];
+        cnt[p] = make_uint2(c.x + 1u, c.y + n_u);
+    }
+}
+
+// Selection: is pixel p active? (rt_ffi.h rt_accum_select; tests/adapt_ref.py restates it operation by operation)
+__device__ __forceinline__ bool select_active(const double2* __restrict__ S, const float4* __restrict__ var,
+                                              const uint2* __restrict__ cnt, double N, int width, int height,
+                                              double abs_tol, double rel_tol, int32_t max_n, long p) {
+    const int row = (int)(p / width), col = (int)(p - (long)row * width);
+    double num = 0., den = 0.;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int r = row + dy, c = col + dx;
+            if (r < 0 || r >= height || c < 0 || c >= width) continue;
+            const double kk = (dx == 0 ? 0.5 : 0.25) * (dy == 0 ? 0.5 : 0.25);
+            num = num + kk * (double)var[(long)r * width + c].w;
+            den = den + kk;
+        }
+    }
+    const double g = num / den;
+    uint32_t n_p = 0;
+    double Np = N;
+    if (cnt) {
+        n_p = cnt[p].y;
+        Np = (double)n_p;
+    }
+    double m[12];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double2 s = S[(size_t)p * 6 + k];
+        m[2 * k] = s.x / Np;
+        m[2 * k + 1] = s.y / Np;
+    }
+    double c3[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double a = 0.;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double mj = m[3 * j + c];
+            a = a + (mj < 0. ? 0. : (mj > 1. ? 1. : mj)) * 0.25;
+        }
+        c3[c] = a;
+    }
+    const double y = (c3[0] + c3[1]) + c3[2];
+    const double thr = (rel_tol * y) / 3.0 + abs_tol;
+    const bool under = max_n <= 0 || (cnt ? (int64_t)n_p : (int64_t)N) < (int64_t)max_n;
+    return g > thr * thr && under;
+}
+
+// Pass 1: each wave's ballot of active pixels (masks[wave], 64 pixels per wave) and each block's count.
+__global__ __launch_bounds__(256) void k_select_count(const double2* __restrict__ S, const float4* __restrict__ var,
+                                                      const uint2* __restrict__ cnt, double N, int width, int height,
+                                                      double abs_tol, double rel_tol, int32_t max_n,
+                                                      unsigned long long* __restrict__ masks,
+                                                      uint32_t* __restrict__ block_count) {
+    __shared__ uint32_t s_n[4];
+    const long npix = (long)width * height;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool act = p < npix && select_active(S, var, cnt, N, width, height, abs_tol, rel_tol, max_n, p);
+    const unsigned long long mk = __ballot(act);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        masks[(size_t)blockIdx.x * 4 + wave] = mk;
+        s_n[wave] = (uint32_t)__popcll(mk);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) block_count[blockIdx.x] = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+}
+
+// Pass 2 (one block of 1024 threads): the exclusive scan of the block counts, in place; *total = their sum. Each thread
+// sums a contiguous segment, the 1024 segment sums are scanned in LDS, then each thread writes its segment's offsets.
+__global__ __launch_bounds__(1024) void k_select_scan(uint32_t* __restrict__ block_count, long nblocks,
+                                                      uint32_t* __restrict__ total) {
+    __shared__ uint32_t s_sum[1024];
+    const long per = (nblocks + 1023) / 1024;
+    const long b0 = min((long)threadIdx.x * per, nblocks), b1 = min(b0 + per, nblocks);
+    uint32_t sum = 0;
+    for (long b = b0; b < b1; ++b) sum += block_count[b];
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {  // Hillis-Steele, inclusive
+        const uint32_t add = threadIdx.x >= (unsigned)off ? s_sum[threadIdx.x - off] : 0u;
+        __syncthreads();
+        s_sum[threadIdx.x] += add;
+        __syncthreads();
+    }
+    uint32_t run = s_sum[threadIdx.x] - sum;  // exclusive
+    for (long b = b0; b < b1; ++b) {
+        const uint32_t c = block_count[b];
+        block_count[b] = run;
+        run += c;
+    }
+    if (threadIdx.x == 1023) *total = s_sum[1023];
+}
+
+// Pass 3: ballot-prefix writes, ascending: block offset + the block's earlier waves + the lanes below.
+__global__ __launch_bounds__(256) void k_select_write(const unsigned long long* __restrict__ masks,
+                                                      const uint32_t* __restrict__ block_off, long npix,
+                                                      uint32_t* __restrict__ out, long cap) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const unsigned long long* mb = masks + (size_t)blockIdx.x * 4;
+    long at = block_off[blockIdx.x];
+    for (int w = 0; w < wave; ++w) at += __popcll(mb[w]);
+    const unsigned long long mk = mb[wave];
+    if (!((mk >> lane) & 1ull) || p >= npix) return;
+    at += __popcll(lane ? (mk & ((~0ull) >> (64 - lane))) : 0ull);
+    if (at < cap) out[at] = (uint32_t)p;
+}
+
+static long select_blocks(long npix) { return (npix + 255) / 256; }
+
+size_t select_scratch_bytes(long npix) {
+    const size_t nb = (size_t)select_blocks(npix);
+    return nb * 4 * sizeof(unsigned long long) + (nb + 2) * sizeof(uint32_t);  // masks | block counts
+}
+
+hipError_t launch_accum_select(const double* S, const float* var, const uint32_t* cnt, int64_t N, int width, int height,
+                               float abs_tol, float rel_tol, int32_t max_n, void* scratch, uint32_t* out, long cap,
+                               uint32_t* total, hipStream_t st) {
+    const long npix = (long)width * height;
+    if (npix <= 0) return hipErrorInvalidValue;
+    const long nb = select_blocks(npix);
+    unsigned long long* masks = (unsigned long long*)scratch;
+    uint32_t* counts = (uint32_t*)(masks + (size_t)nb * 4);
+    hipLaunchKernelGGL(k_select_count, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<const double2*>(S),
+                       reinterpret_cast<const float4*>(var), reinterpret_cast<const uint2*>(cnt), (double)N, width,
+                       height, (double)abs_tol, (double)rel_tol, max_n, masks, counts);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, st, counts, nb, total);
+    if (cap > 0 && out)
+        hipLaunchKernelGGL(k_select_write, dim3((unsigned)nb), dim3(256), 0, st, masks, counts, npix, out, cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_accum_cnt_fill(uint32_t* cnt, long npix, uint32_t K, uint32_t N, bool add, hipStream_t st) {
+    if (npix <= 0) return hipSuccess;
+    const long blocks = (npix + 255) / 256;
+    if (add)
+        hipLaunchKernelGGL(k_accum_cnt_fill<true>, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<uint2*>(cnt),
+                           npix, K, N);
+    else
+        hipLaunchKernelGGL(k_accum_cnt_fill<false>, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<uint2*>(cnt),
+                           npix, K, N);
+    return hipGetLastError();
+}
+
+hipError_t launch_accum_add_list(double* S, double* Q, uint32_t* cnt, const uint32_t* list, long n_list, const double* m,
+                                 int32_t n, hipStream_t st) {
+    const long npairs = n_list * 6;
+    if (npairs <= 0) return hipSuccess;
+    const long blocks = (npairs + 255) / 256;
+    if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_accum_add_list, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<double2*>(S),
+                       reinterpret_cast<double2*>(Q), reinterpret_cast<uint2*>(cnt), list,
+                       reinterpret_cast<const double2*>(m), npairs, (double)n, (uint32_t)n);
+    return hipGetLastError();
+}
+
 hipError_t launch_accum_add(double* S, double* Q, const double* m, long npix, int32_t n, bool first, hipStream_t st) {
     const long npairs = npix * 6;
     if (npairs <= 0) return hipSuccess;
@@ -90,6 +305,16 @@ hipError_t launch_accum_resolve(const double* S, const double* Q, long npix, int
     const long blocks = (npix + 255) / 256;
     hipLaunchKernelGGL(k_accum_resolve, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const double2*>(S),
                        reinterpret_cast<const double2*>(Q), npix, (double)N, (double)(K - 1),
+                       reinterpret_cast<double2*>(sub), reinterpret_cast<float4*>(var));
+    return hipGetLastError();
+}
+
+hipError_t launch_accum_resolve_cnt(const double* S, const double* Q, const uint32_t* cnt, long npix, double* sub,
+                                    float* var, hipStream_t st) {
+    if (npix <= 0 || (!sub && !var)) return hipSuccess;
+    const long blocks = (npix + 255) / 256;
+    hipLaunchKernelGGL(k_accum_resolve_cnt, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const double2*>(S),
+                       reinterpret_cast<const double2*>(Q), reinterpret_cast<const uint2*>(cnt), npix,
                        reinterpret_cast<double2*>(sub), reinterpret_cast<float4*>(var));
     return hipGetLastError();
 }

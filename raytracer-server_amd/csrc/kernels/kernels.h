@@ -77,6 +77,12 @@ int diag_read_flat(unsigned long long* cnt16, unsigned long long* reg32, unsigne
 hipError_t launch_megakernel_f32(const DevScene& sc, const RenderArgs& a, double* sub_buf, uint32_t* next_sub,
                                  hipStream_t st);
 hipError_t launch_finalize_f64(const RenderArgs& a, const double* sub_buf, hipStream_t st);
+// Pixel-list render (render_list_f64.hip): the subpixel means of the n_pixels frame pixels
+// pixels[e] = row * width + col (device, unique ids < width * height) into sub_buf[e][4][3], with the fused
+// megakernel's per-vertex code and Cfg choice (a.features & 15); a.tw / th / x0 / y0 / row_step play no part.
+// n_pixels * 4 <= INT32_MAX. next_unit: the ticket counter (reset here).
+hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
+                                  double* sub_buf, uint32_t* next_unit, hipStream_t st);
 hipError_t launch_trace_f64(const DevScene& sc, long n, const double* o, const double* d, double* t, int32_t* obj,
                             double* pos, double* nrm, bool mesh_nearest, hipStream_t st);
 

@@ -988,18 +988,9 @@ struct PendingStats {
     }
 };
 
-// Enqueue one render on `st` (device buffers); returns without waiting for the device (except in
-// wavefront mode, whose host loop drives the bounces and polls host_cancel). dcancel: device view of
-// a cancel word the megakernels poll (CancelMirror::dev) or null; ps: stats to complete after the
-// stream drains (PendingStats::finish) or null.
-int render_enqueue(rt_scene* s, const rt_render_params* p, uint8_t* d_rgb, double* d_sub, hipStream_t st,
-                   const int32_t* dcancel, const volatile int32_t* host_cancel, PendingStats* ps) {
-    int rc = check_params(p);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    rt::DevScene ds;
-    rc = upload(s, p->device, &ds);
-    if (rc != RT_OK) return rc;
+// The kernels' view of `p` on the uploaded scene `ds`: frame, tile, samples, seed, camera frame and the Cfg<F>
+// feature bits (no output pointers, no scheduling).
+rt::RenderArgs make_render_args(const rt_scene* s, const rt_render_params* p, const rt::DevScene& ds) {
     rt::RenderArgs a{};
     a.width = p->width;
     a.height = p->height;
@@ -1026,6 +1017,22 @@ int render_enqueue(rt_scene* s, const rt_render_params* p, uint8_t* d_rgb, doubl
     a.seed = p->seed;
     rt::host::camera_frame(s->host, p->width, p->height, a.cx, a.cy);
     a.inv_n = a.n_samples > 0 ? 1. / (double)a.n_samples : 0.0;
+    return a;
+}
+
+// Enqueue one render on `st` (device buffers); returns without waiting for the device (except in
+// wavefront mode, whose host loop drives the bounces and polls host_cancel). dcancel: device view of
+// a cancel word the megakernels poll (CancelMirror::dev) or null; ps: stats to complete after the
+// stream drains (PendingStats::finish) or null.
+int render_enqueue(rt_scene* s, const rt_render_params* p, uint8_t* d_rgb, double* d_sub, hipStream_t st,
+                   const int32_t* dcancel, const volatile int32_t* host_cancel, PendingStats* ps) {
+    int rc = check_params(p);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    rt::DevScene ds;
+    rc = upload(s, p->device, &ds);
+    if (rc != RT_OK) return rc;
+    rt::RenderArgs a = make_render_args(s, p, ds);
     a.sub_out = d_sub;
     a.rgb_out = d_rgb;
     const bool fp32 = (p->flags & RT_FLAG_FP32) != 0;
@@ -1676,6 +1683,11 @@ struct rt_accum {
     double* S = nullptr;
     double* Q = nullptr;
     char* stage = nullptr;
+    // rendering to an error target: the per-pixel counts cnt[pix][2] = (K_p, N_p) head a buffer made by
+    // the first sparse merge or selection; they are valid (and used) once a sparse pass has been merged
+    char* adapt = nullptr;
+    bool sparse = false;
+    uint32_t* cnt() const { return (uint32_t*)adapt; }
     size_t npix() const { return (size_t)width * height; }
     size_t sub_bytes() const { return npix() * 12 * sizeof(double); }
     double* stage_sub() const { return (double*)stage; }
@@ -1723,6 +1735,7 @@ int accum_ready(rt_accum* a, bool sums, bool stage) {
 // Merges the pass in d_sub on `st`, waits for it and counts it.
 int accum_merge(rt_accum* a, const double* d_sub, int32_t n, hipStream_t st) {
     hipError_t e = rt::launch_accum_add(a->S, a->Q, d_sub, (long)a->npix(), n, a->K == 0, st);
+    if (e == hipSuccess && a->sparse) e = rt::launch_accum_cnt_fill(a->cnt(), (long)a->npix(), 1u, (uint32_t)n, true, st);
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum merge: ") + hipGetErrorString(e));
@@ -1757,7 +1770,8 @@ int check_accum_resolve(const char* who, const rt_accum* a, const void* var) {
 
 // Enqueues the resolve on `st`: sub (or, when only the RGB8 is wanted, the staging sub), var, rgb.
 hipError_t accum_resolve_enqueue(rt_accum* a, double* d_sub, float* d_var, uint8_t* d_rgb, hipStream_t st) {
-    hipError_t e = rt::launch_accum_resolve(a->S, a->Q, (long)a->npix(), a->N, a->K, d_sub, d_var, st);
+    hipError_t e = a->sparse ? rt::launch_accum_resolve_cnt(a->S, a->Q, a->cnt(), (long)a->npix(), d_sub, d_var, st)
+                             : rt::launch_accum_resolve(a->S, a->Q, (long)a->npix(), a->N, a->K, d_sub, d_var, st);
     if (e == hipSuccess && d_rgb) {
         rt::RenderArgs ra{};
         ra.tw = a->width;
@@ -1816,10 +1830,11 @@ int rt_accum_create(int32_t device, int32_t width, int32_t height, void** out) {
 void rt_accum_destroy(void* accum) {
     rt_accum* a = (rt_accum*)accum;
     if (!a) return;
-    if (a->S || a->stage) {
+    if (a->S || a->stage || a->adapt) {
         (void)hipSetDevice(a->device);
         if (a->S) (void)hipFree(a->S);
         if (a->stage) (void)hipFree(a->stage);
+        if (a->adapt) (void)hipFree(a->adapt);
     }
     delete a;
 }
@@ -1829,6 +1844,7 @@ int rt_accum_reset(void* accum) {
     if (!a) return fail(RT_E_INVAL, "rt_accum_reset: null argument");
     a->K = 0;  // the next pass stores without reading
     a->N = 0;
+    a->sparse = false;  // the per-pixel counts are forgotten with the passes
     return RT_OK;
 }
 
@@ -1995,6 +2011,373 @@ int rt_denoise_var(int32_t device, int32_t width, int32_t height, const double* 
     (void)hipFree(buf);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_denoise_var: ") + hipGetErrorString(e));
     return rc < 0 ? fail(rc, err) : rc;
+}
+
+// Rendering to a per-pixel error target ---------------------------------------------------
+
+namespace {
+
+// The arguments of a pixel-list render that need no device: the whole frame, the f64 fused path, the list's size.
+int check_render_pixels(const char* who, const rt_scene* scene, const rt_render_params* p, const void* pixels,
+                        int64_t n_pixels) {
+    const std::string w(who);
+    if (!scene || !p) return fail(RT_E_INVAL, w + ": null argument");
+    const int rc = check_params(p);
+    if (rc != RT_OK) return rc;
+    if (p->x0 != 0 || p->y0 != 0 || p->tile_w != p->width || p->tile_h != p->height)
+        return fail(RT_E_INVAL, w + ": params must be the whole frame");
+    if (p->row_step > 1) return fail(RT_E_INVAL, w + ": row_step must be 0 or 1");
+    if (p->flags & (RT_FLAG_FP32 | RT_FLAG_MESH_NEAREST))
+        return fail(RT_E_INVAL, w + ": RT_FLAG_FP32 and RT_FLAG_MESH_NEAREST are not supported by the pixel-list render");
+    if (n_pixels < 0 || n_pixels > (int64_t)p->width * p->height)
+        return fail(RT_E_INVAL, w + ": n_pixels must be in 0 .. width * height");
+    if (n_pixels > (int64_t)INT32_MAX / 4) return fail(RT_E_INVAL, w + ": n_pixels * 4 must fit an int32");
+    if (n_pixels > 0 && !pixels) return fail(RT_E_INVAL, w + ": null pixel list");
+    return RT_OK;
+}
+
+// A host pixel list: strictly ascending (so unique) ids below npix.
+int check_pixel_list(const char* who, const uint32_t* pixels, int64_t n_pixels, int64_t npix) {
+    for (int64_t e = 0; e < n_pixels; ++e) {
+        if ((int64_t)pixels[e] >= npix)
+            return fail(RT_E_INVAL, std::string(who) + ": pixel id " + std::to_string(pixels[e]) + " outside the frame");
+        if (e > 0 && pixels[e] <= pixels[e - 1])
+            return fail(RT_E_INVAL, std::string(who) + ": the pixel list must be strictly ascending");
+    }
+    return RT_OK;
+}
+
+// render_enqueue for a pixel list (k_render_list_f64 + k_finalize_f64 on the compact buffer); arguments checked by
+// check_render_pixels, n_pixels > 0. d_rgb and d_sub may be null.
+int render_pixels_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t* d_pixels, int64_t n_pixels,
+                          uint8_t* d_rgb, double* d_sub, hipStream_t st, const int32_t* dcancel, PendingStats* ps) {
+    HIP_TRY(hipSetDevice(p->device));
+    rt::DevScene ds;
+    const int rc = upload(s, p->device, &ds);
+    if (rc != RT_OK) return rc;
+    rt::RenderArgs a = make_render_args(s, p, ds);
+    a.x0 = 0;
+    a.y0 = 0;
+    a.row_step = 1;
+    a.tw = (int32_t)n_pixels;  // k_finalize_f64's view of the compact buffer
+    a.th = 1;
+    a.rgb_out = d_rgb;
+    a.cancel = dcancel;
+    if (ps) {
+        const hipError_t e = ps->init(ps->out);
+        if (e != hipSuccess) return fail(RT_E_HIP, std::string("stats: ") + hipGetErrorString(e));
+        ps->samples = n_pixels * 4 * (int64_t)a.n_samples;
+        HIP_TRY(hipEventRecord(ps->e0, st));
+    }
+    hipError_t te;
+    std::unique_ptr<rt::Workspace> ws = take_workspace(s, p->device, st, &te);
+    if (!ws) return fail(RT_E_HIP, std::string("workspace: ") + hipGetErrorString(te));
+    hipError_t e = ws->ensure_counters();
+    double* sub = d_sub;
+    if (e == hipSuccess && !sub) {
+        e = ws->ensure_sub((size_t)n_pixels);
+        sub = ws->sub_buf;
+    }
+    a.sub_out = sub;
+    if (e == hipSuccess && ps) e = hipMemsetAsync(ws->counters, 0, 8 * sizeof(unsigned long long), st);
+    if (e == hipSuccess && a.n_samples <= 0) e = hipMemsetAsync(sub, 0, (size_t)n_pixels * 12 * sizeof(double), st);
+    if (e == hipSuccess) {
+        a.counters = ps ? ws->counters : nullptr;
+        e = rt::launch_render_list_f64(ds, a, d_pixels, (long)n_pixels, sub, (uint32_t*)(ws->counters + 4), st);
+    }
+    if (e == hipSuccess && d_rgb) e = rt::launch_finalize_f64(a, sub, st);
+    if (e == hipSuccess && ps) e = hipEventRecord(ps->e1, st);
+    if (e == hipSuccess && ps) e = hipMemcpyAsync(ps->count, ws->counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    give_workspace(s, std::move(ws), st);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("pixel-list render: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// The accumulator's error-target buffers: cnt | list | selection scratch | total.
+// (the scratch and the total 16-byte aligned; the scratch holds 8-byte words)
+size_t adapt_scratch_at(const rt_accum* a) { return align_up(a->npix() * 12, 16); }
+size_t adapt_total_at(const rt_accum* a) {
+    return adapt_scratch_at(a) + align_up(rt::select_scratch_bytes((long)a->npix()), 16);
+}
+size_t adapt_bytes(const rt_accum* a) { return adapt_total_at(a) + 16; }
+uint32_t* adapt_list(const rt_accum* a) { return (uint32_t*)(a->adapt + a->npix() * 8); }
+void* adapt_scratch(const rt_accum* a) { return a->adapt + adapt_scratch_at(a); }
+uint32_t* adapt_total(const rt_accum* a) { return (uint32_t*)(a->adapt + adapt_total_at(a)); }
+int adapt_ready(rt_accum* a) {
+    if (a->adapt) return RT_OK;
+    const hipError_t e = hipMalloc((void**)&a->adapt, adapt_bytes(a));
+    if (e != hipSuccess) {
+        a->adapt = nullptr;
+        return oom_or_hip(e, "rt_accum error-target buffers");
+    }
+    return RT_OK;
+}
+
+// host_list: the list is on the host and checked (strictly ascending ids below width * height).
+int check_sparse(const char* who, const rt_accum* a, const void* pixels, int64_t n_pixels, bool host_list) {
+    const std::string w(who);
+    if (!a) return fail(RT_E_INVAL, w + ": null argument");
+    if (n_pixels < 0 || n_pixels > (int64_t)a->npix()) return fail(RT_E_INVAL, w + ": n_pixels must be in 0 .. width * height");
+    if (n_pixels > 0 && !pixels) return fail(RT_E_INVAL, w + ": null pixel list");
+    if (host_list) {
+        const int rc = check_pixel_list(who, (const uint32_t*)pixels, n_pixels, (int64_t)a->npix());
+        if (rc != RT_OK) return rc;
+    }
+    if (a->K < 2) return fail(RT_E_INVAL, w + ": a sparse pass needs two full-frame passes first");
+    return RT_OK;
+}
+
+// Merges the compact pass d_sub of the device list d_pixels on `st` and waits for it; the first sparse merge fills the
+// per-pixel counts with the frame's (K, N).
+int accum_merge_list(rt_accum* a, const uint32_t* d_pixels, int64_t n_pixels, const double* d_sub, int32_t n,
+                     hipStream_t st) {
+    hipError_t e = hipSuccess;
+    if (!a->sparse) e = rt::launch_accum_cnt_fill(a->cnt(), (long)a->npix(), (uint32_t)a->K, (uint32_t)a->N, false, st);
+    if (e == hipSuccess) e = rt::launch_accum_add_list(a->S, a->Q, a->cnt(), d_pixels, (long)n_pixels, d_sub, n, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum sparse merge: ") + hipGetErrorString(e));
+    a->sparse = true;
+    return RT_OK;
+}
+
+int check_select(const char* who, const rt_accum* a, float abs_tol, float rel_tol, int64_t cap, const void* out,
+                 const int64_t* n_out) {
+    const std::string w(who);
+    if (!a || !n_out) return fail(RT_E_INVAL, w + ": null argument");
+    if (!(abs_tol >= 0.f) || !(rel_tol >= 0.f)) return fail(RT_E_INVAL, w + ": tolerances must be >= 0 and not NaN");
+    if (cap < 0 || (cap > 0 && !out)) return fail(RT_E_INVAL, w + ": bad output buffer");
+    if (a->K < 2) return fail(RT_E_INVAL, w + ": the selection needs at least two passes");
+    return RT_OK;
+}
+
+// Resolves the variance into the staging area, selects into d_out (device, cap ids) on `st`, waits, and reads the count.
+int select_run(rt_accum* a, float abs_tol, float rel_tol, int32_t max_n, uint32_t* d_out, int64_t cap, int64_t* n_out,
+               hipStream_t st) {
+    hipError_t e = accum_resolve_enqueue(a, nullptr, a->stage_var(), nullptr, st);
+    if (e == hipSuccess)
+        e = rt::launch_accum_select(a->S, a->stage_var(), a->sparse ? a->cnt() : nullptr, a->N, a->width, a->height,
+                                    abs_tol, rel_tol, max_n, adapt_scratch(a), d_out, (long)cap, adapt_total(a), st);
+    uint32_t total = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, adapt_total(a), sizeof total, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_select: ") + hipGetErrorString(e));
+    *n_out = (int64_t)total;
+    return RT_OK;
+}
+
+}  // namespace
+
+int rt_render_pixels_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
+                            int64_t n_pixels, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats) {
+    int rc = check_render_pixels("rt_render_pixels_device", scene, params, d_pixels, n_pixels);
+    if (rc != RT_OK) return rc;
+    if (n_pixels == 0) {
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    rc = need_device("rt_render_pixels_device", params->device);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    PendingStats ps;
+    ps.out = stats;
+    rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), params, (const uint32_t*)d_pixels, n_pixels, (uint8_t*)d_rgb,
+                               (double*)d_sub, st, nullptr, stats ? &ps : nullptr);
+    if (rc < 0 || !stats) return rc;
+    const hipError_t e = hipStreamSynchronize(st);  // stats: synchronous with respect to the stream (rt_ffi.h)
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("stats sync: ") + hipGetErrorString(e));
+    std::string err;
+    const int f = ps.finish(&err);
+    return f < 0 ? fail(f, err) : rc;
+}
+
+int rt_render_pixels(const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels, int64_t n_pixels,
+                     uint8_t* rgb_out, double* sub_out, const volatile int32_t* cancel, rt_render_stats* stats) {
+    int rc = check_render_pixels("rt_render_pixels", scene, p, pixels, n_pixels);
+    if (rc == RT_OK) rc = check_pixel_list("rt_render_pixels", pixels, n_pixels, (int64_t)p->width * p->height);
+    if (rc != RT_OK) return rc;
+    if (n_pixels == 0) {
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    rc = need_device("rt_render_pixels", p->device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n = (size_t)n_pixels;
+    const size_t b_sub = n * 12 * sizeof(double), b_pix = align_up(n * sizeof(uint32_t), 16);
+    // one allocation: sub | pixels | rgb (each part 16-byte aligned)
+    char* buf = nullptr;
+    hipError_t e = hipMalloc((void**)&buf, b_sub + b_pix + align_up(n * 3, 16));
+    if (e != hipSuccess) return oom_or_hip(e, "rt_render_pixels buffers");
+    double* d_sub = (double*)buf;
+    uint32_t* d_pix = (uint32_t*)(buf + b_sub);
+    uint8_t* d_rgb = (uint8_t*)(buf + b_sub + b_pix);
+    std::string err;
+    {
+        CallStream cs;  // waited for and destroyed before the buffers are freed
+        CancelMirror mirror;
+        e = cs.init();
+        if (e == hipSuccess && cancel) e = mirror.init();
+        hipStream_t st = cs.st;
+        if (e == hipSuccess) e = hipMemcpyAsync(d_pix, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) {
+            rc = RT_E_HIP;
+            err = std::string("rt_render_pixels: ") + hipGetErrorString(e);
+        }
+        rt_render_stats local;
+        PendingStats ps;
+        ps.out = stats ? stats : &local;
+        if (rc == RT_OK) {
+            rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), p, d_pix, n_pixels, rgb_out ? d_rgb : nullptr, d_sub, st,
+                                       mirror.dev, &ps);
+            err = g_err;
+        }
+        if (rc == RT_OK) {
+            // as rt_render: wait for the render while relaying the cancel flag, then copy back
+            e = wait_stream(st, cancel, &mirror);
+            if (e == hipSuccess && rgb_out) e = hipMemcpyAsync(rgb_out, d_rgb, n * 3, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && sub_out) e = hipMemcpyAsync(sub_out, d_sub, b_sub, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_render_pixels readback: ") + hipGetErrorString(e); }
+            if (rc == RT_OK) {
+                const int f = ps.finish(&err);
+                if (f < 0) rc = f;
+            }
+            if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
+        }
+    }
+    (void)hipFree(buf);
+    return rc < 0 ? fail(rc, err) : rc;
+}
+
+int rt_accum_add_pixels(void* accum, const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels,
+                        int64_t n_pixels, const volatile int32_t* cancel, rt_render_stats* stats) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_accum_add(a, scene, p);
+    if (rc == RT_OK) rc = check_render_pixels("rt_accum_add_pixels", scene, p, pixels, n_pixels);
+    if (rc == RT_OK) rc = check_sparse("rt_accum_add_pixels", a, pixels, n_pixels, true);
+    if (rc != RT_OK) return rc;
+    if (n_pixels == 0) {
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    rc = need_device("rt_accum_add_pixels", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc != RT_OK) return rc;
+    CallStream cs;  // destroyed last: after the stats' events and the cancel word have gone back
+    hipError_t ce = cs.init();
+    CancelMirror mirror;
+    if (ce == hipSuccess && cancel) ce = mirror.init();
+    hipStream_t st = cs.st;
+    if (ce == hipSuccess) ce = hipMemcpyAsync(adapt_list(a), pixels, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (ce != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_add_pixels: ") + hipGetErrorString(ce));
+    rt_render_stats local;
+    PendingStats ps;
+    ps.out = stats ? stats : &local;
+    rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), p, adapt_list(a), n_pixels, nullptr, a->stage_sub(), st,
+                               mirror.dev, &ps);
+    std::string err = g_err;
+    if (rc == RT_OK) {
+        const hipError_t e = wait_stream(st, cancel, &mirror);
+        if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_accum_add_pixels: ") + hipGetErrorString(e); }
+        if (rc == RT_OK) {
+            const int f = ps.finish(&err);
+            if (f < 0) rc = f;
+        }
+        if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
+    } else {
+        (void)hipStreamSynchronize(st);
+    }
+    if (rc < 0) return fail(rc, err);
+    if (rc != RT_OK) return rc;  // cancelled: nothing merged
+    return accum_merge_list(a, adapt_list(a), n_pixels, a->stage_sub(), p->spp / 4, st);
+}
+
+int rt_accum_add_sub_pixels(void* accum, const uint32_t* pixels, int64_t n_pixels, const double* sub, int32_t n) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = RT_OK;
+    if (n < 1) rc = fail(RT_E_INVAL, "rt_accum_add_sub_pixels: n must be >= 1");
+    if (rc == RT_OK && n_pixels > 0 && !sub) rc = fail(RT_E_INVAL, "rt_accum_add_sub_pixels: null argument");
+    if (rc == RT_OK) rc = check_sparse("rt_accum_add_sub_pixels", a, pixels, n_pixels, true);
+    if (rc != RT_OK || n_pixels == 0) return rc;
+    rc = need_device("rt_accum_add_sub_pixels", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc != RT_OK) return rc;
+    CallStream cs;
+    HIP_TRY(cs.init());
+    HIP_TRY(hipMemcpyAsync(adapt_list(a), pixels, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, cs.st));
+    HIP_TRY(hipMemcpyAsync(a->stage_sub(), sub, (size_t)n_pixels * 12 * sizeof(double), hipMemcpyHostToDevice, cs.st));
+    return accum_merge_list(a, adapt_list(a), n_pixels, a->stage_sub(), n, cs.st);
+}
+
+int rt_accum_add_sub_pixels_device(void* accum, const void* d_pixels, int64_t n_pixels, const void* d_sub, int32_t n,
+                                   void* stream) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = RT_OK;
+    if (n < 1) rc = fail(RT_E_INVAL, "rt_accum_add_sub_pixels_device: n must be >= 1");
+    if (rc == RT_OK && n_pixels > 0 && !d_sub) rc = fail(RT_E_INVAL, "rt_accum_add_sub_pixels_device: null argument");
+    if (rc == RT_OK) rc = check_sparse("rt_accum_add_sub_pixels_device", a, d_pixels, n_pixels, false);
+    if (rc != RT_OK || n_pixels == 0) return rc;
+    rc = need_device("rt_accum_add_sub_pixels_device", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, false);
+    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc != RT_OK) return rc;
+    return accum_merge_list(a, (const uint32_t*)d_pixels, n_pixels, (const double*)d_sub, n, (hipStream_t)stream);
+}
+
+int rt_accum_counts(void* accum, uint32_t* k_out, uint32_t* n_out) {
+    rt_accum* a = (rt_accum*)accum;
+    if (!a) return fail(RT_E_INVAL, "rt_accum_counts: null argument");
+    const size_t npix = a->npix();
+    if (!a->sparse) {  // one K and N for the frame: no device call
+        for (size_t i = 0; i < npix; ++i) {
+            if (k_out) k_out[i] = (uint32_t)a->K;
+            if (n_out) n_out[i] = (uint32_t)a->N;
+        }
+        return RT_OK;
+    }
+    int rc = need_device("rt_accum_counts", a->device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(a->device));
+    std::vector<uint32_t> both(npix * 2);
+    HIP_TRY(hipMemcpy(both.data(), a->cnt(), npix * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; ++i) {
+        if (k_out) k_out[i] = both[2 * i];
+        if (n_out) n_out[i] = both[2 * i + 1];
+    }
+    return RT_OK;
+}
+
+int rt_accum_select_device(void* accum, float abs_tol, float rel_tol, int32_t max_n, void* d_pixels, int64_t cap,
+                           int64_t* n_out, void* stream) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_select("rt_accum_select_device", a, abs_tol, rel_tol, cap, d_pixels, n_out);
+    if (rc == RT_OK) rc = need_device("rt_accum_select_device", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc != RT_OK) return rc;
+    return select_run(a, abs_tol, rel_tol, max_n, (uint32_t*)d_pixels, cap, n_out, (hipStream_t)stream);
+}
+
+int rt_accum_select(void* accum, float abs_tol, float rel_tol, int32_t max_n, uint32_t* pixels_out, int64_t cap,
+                    int64_t* n_out) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_select("rt_accum_select", a, abs_tol, rel_tol, cap, pixels_out, n_out);
+    if (rc == RT_OK) rc = need_device("rt_accum_select", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc != RT_OK) return rc;
+    CallStream cs;
+    HIP_TRY(cs.init());
+    const int64_t dcap = std::min<int64_t>(cap, (int64_t)a->npix());  // the list buffer holds every pixel
+    rc = select_run(a, abs_tol, rel_tol, max_n, adapt_list(a), dcap, n_out, cs.st);
+    if (rc != RT_OK) return rc;
+    const int64_t n = std::min(*n_out, dcap);
+    if (n > 0) HIP_TRY(hipMemcpy(pixels_out, adapt_list(a), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 // Batch query diagnostics (include/rt_diag.h, kernels/diag_queries.h) -------------------------------------

@@ -15,6 +15,8 @@ Run:  PORT=8080 python -m rt_amd.server <scenes dir>
       RT_DENOISE=<levels> selects denoised previews (whole frames through rt_amd.render_denoised).
       RT_PROGRESSIVE=<first_spp> selects progressive jobs (whole frames through rt_amd.render_progressive, each refined
       frame re-sent with the same chunk messages).
+      RT_TARGET_ERROR=<abs_tol> selects jobs rendered to a per-pixel error target (rt_amd.render_to_error, DESIGN.md
+      §13): RT_PROGRESSIVE gives the first frame's spp, the request's spp is the per-pixel budget.
 """
 import asyncio
 import ctypes
@@ -154,6 +156,57 @@ class ProgressiveJob:
             frames.close()
 
 
+class AdaptiveJob:
+    """A whole-frame job that renders to a per-pixel error target (rt_amd.render_to_error): two full
+    passes, then sparse passes over the pixels whose estimated error is still above abs_tol, until none is left or every
+    such pixel holds the request's spp. Every refined frame is sent again with the same chunk messages, as
+    ProgressiveJob does. RenderJob's interface: a stop takes effect between passes, and inside a pass through the cancel
+    word."""
+
+    def __init__(self, send, abs_tol, first=16, device=0, **denoise_params):
+        self.send = send
+        self.abs_tol = abs_tol
+        self.first = first
+        self.device = device
+        self.denoise_params = denoise_params
+        self.cancel = ctypes.c_int32(1)  # starts cancelled == not running
+
+    def running(self):
+        return self.cancel.value == 0
+
+    def stop(self):
+        self.cancel.value = 1
+
+    async def run(self, scene, width, height, spp, seed):
+        """spp is the per-pixel budget. Returns True when stopped before the last frame was sent."""
+        import rt_amd
+
+        self.cancel.value = 0
+        loop = asyncio.get_running_loop()
+        frames = rt_amd.render_to_error(scene, width, height, abs_tol=self.abs_tol, max_spp=max(spp, self.first),
+                                        first=self.first, seed=seed, device=self.device, cancel=self.cancel,
+                                        **self.denoise_params)
+        try:
+            while True:
+                if self.cancel.value:
+                    return True
+                frame = await loop.run_in_executor(None, next, frames, None)
+                if frame is None or self.cancel.value:
+                    return True
+                rgb, _, active = frame
+                for msg in chunk_messages(rgb, 0):
+                    try:
+                        await self.send(msg)
+                    except ConnectionError:
+                        self.cancel.value = 1
+                        return True
+                if active == 0.0:  # nothing left above the target or below the budget: the last frame
+                    self.cancel.value = 1
+                    return False
+        finally:
+            frames.close()
+
+
 class Server:
     def __init__(self, scenes, renderer=None, width=WIDTH, height=HEIGHT, band_rows=32, log=print, job_factory=None):
         self.scenes = scenes
@@ -246,7 +299,14 @@ def main(argv=None):
         # (geometry.rs:886-903), not the reference's first-hit octree walk (geometry.rs:1237-1295)
         print("RT_PRECISION=f32: f32 perf mode; meshes (flying_unicorn) use nearest-triangle hits, not the "
               "reference's octree semantics; frames differ statistically from server.rs", file=sys.stderr)
-    if "RT_PROGRESSIVE" in os.environ:
+    if "RT_TARGET_ERROR" in os.environ:
+        # rendering to an error target: whole frames, sparse passes over the pixels still above it
+        abs_tol = float(os.environ["RT_TARGET_ERROR"])
+        first = int(os.environ.get("RT_PROGRESSIVE", rt_amd.ERROR_TARGET_DEFAULTS["first"]))
+        print(f"RT_TARGET_ERROR={abs_tol}: whole-frame jobs rendered to a per-pixel error target, first frame at "
+              f"{first} spp, the request's spp as the per-pixel budget", file=sys.stderr)
+        server = Server(scenes, job_factory=lambda send: AdaptiveJob(send, abs_tol, first=first))
+    elif "RT_PROGRESSIVE" in os.environ:
         # progressive refinement: whole frames, each refined frame re-sent with the same chunk messages
         first = int(os.environ["RT_PROGRESSIVE"])
         print(f"RT_PROGRESSIVE={first}: whole-frame progressive jobs, first frame at {first} spp, variance-guided "

@@ -1,0 +1,229 @@
+"""Cost and benefit of rendering to a per-pixel error target on the GPU.
+
+  python tools/adapt_probe.py time [--size 1920x1080] [--reps 30] [--log profiles/adapt_time.log]
+      cornell_box at 16 spp, HIP events (torch.cuda.Event on the stream the calls are enqueued on) in one process, after
+      a warm-up and as the median of --reps calls: rt_render_pixels_device for lists of 100 %, 50 %, 10 % and 1 % of the
+      pixels, both every k-th pixel and the ids rt_accum_select returns at the threshold that leaves that fraction
+      active, each interleaved with rt_render_device of the full frame at 16 spp; then rt_accum_select_device and
+      rt_accum_add_sub_pixels_device. Reports Msamples/s, the 100 % list's rate over the full-frame megakernel's, and the
+      break-even fraction (the list size at which a sparse pass costs a full pass).
+  python tools/adapt_probe.py target [--size 96x72] [--log profiles/adapt_target.log]
+      The three scenes with abs_tol in {0.03, 0.04, 0.06}: two full 8-spp passes, up to 30 sparse passes of 16 spp; mean
+      and max spp, passes, and the linear RMSE against a 4096-spp frame of seed 999 over that of a uniform accumulation
+      with the same pass sizes taken to the first total at or above the mean spp. These figures choose
+      rt_amd.ERROR_TARGET_DEFAULTS.
+"""
+import argparse
+import ctypes
+import os
+import statistics
+import sys
+
+import numpy as np
+
+import torch  # before rt_amd, as bench.py: the process's HIP runtime is the one torch brings
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "raytracer-server_amd"))
+import rt_amd  # noqa: E402
+
+SCENES = ("cornell_box", "cubes", "flying_unicorn")
+V = ctypes.c_void_p
+
+
+class Log:
+    def __init__(self, path):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self.f = open(path, "w")
+
+    def __call__(self, line=""):
+        print(line, flush=True)
+        self.f.write(line + "\n")
+        self.f.flush()
+
+
+def _scene(name):
+    return rt_amd.Scene.from_toml(os.path.join(REPO, "scenes", f"{name}.toml"))
+
+
+def _size(s):
+    w, h = s.lower().split("x")
+    return int(w), int(h)
+
+
+def _timed_pair(fn_a, fn_b, reps, warm=3):
+    """Medians (ms) of fn_a and fn_b, called alternately between events on torch's current stream."""
+    for _ in range(warm):
+        fn_a()
+        fn_b()
+    torch.cuda.synchronize()
+    out = ([], [])
+    for _ in range(reps):
+        for fn, ms in zip((fn_a, fn_b), out):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+    return statistics.median(out[0]), statistics.median(out[1])
+
+
+def _c_of(sub):
+    px = np.zeros(sub.shape[:2] + (3,))
+    for j in range(4):
+        px = px + np.clip(sub[:, :, j], 0.0, 1.0) * 0.25
+    return px
+
+
+def cmd_time(args):
+    if rt_amd.device_count() < 1:
+        raise RuntimeError("adapt_probe: no HIP device visible (it measures on the GPU only)")
+    log = Log(args.log)
+    w, h = _size(args.size)
+    npix, spp = w * h, 16
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+    st = V(stream) if stream else None
+    sc = _scene("cornell_box")
+    p = rt_amd.make_params(w, h, spp, 0x5EED, None, rt_amd.FLAG_MEGAKERNEL, 0, 1)
+    rgb = torch.zeros(npix * 3, dtype=torch.uint8, device=dev)
+    sub = torch.zeros(npix * 12, dtype=torch.float64, device=dev)
+    lsub = torch.zeros(npix * 12, dtype=torch.float64, device=dev)
+    ids_d = torch.zeros(npix, dtype=torch.int32, device=dev)
+
+    def full():
+        rt_amd.render_device(sc, p, rgb.data_ptr(), sub.data_ptr(), stream)
+
+    def listed(n):
+        def fn():
+            rt_amd._check(rt_amd.lib.rt_render_pixels_device(sc.handle, ctypes.byref(p), V(ids_d.data_ptr()), n, None,
+                                                             V(lsub.data_ptr()), st, None))
+        return fn
+
+    log(f"# adapt_probe time: cornell_box {w}x{h}, {spp} spp, median of {args.reps} (HIP events, one process, "
+        "each list interleaved with the full frame)")
+    # an accumulator with two 8-spp passes: the selection's input
+    acc = rt_amd.Accumulator(w, h)
+    acc.add(sc, 8, 1)
+    acc.add(sc, 8, 2)
+    log("fraction  list            n_pixels   list ms   full ms  list Ms/s  full Ms/s  list/full time")
+    rate100 = None
+    rows = []
+    for frac in (1.0, 0.5, 0.1, 0.01):
+        k = max(1, int(round(1.0 / frac)))
+        strided = np.arange(0, npix, k, dtype=np.uint32)
+        # the threshold that leaves about `frac` of the pixels active: bisect abs_tol on the device's own count
+        lo, hi = 0.0, 1.0
+        for _ in range(30):
+            mid = 0.5 * (lo + hi)
+            n = acc.select(mid, 0.0, 0, cap=0)[1]
+            if n > frac * npix:
+                lo = mid
+            else:
+                hi = mid
+        selected = acc.select(hi if frac < 1.0 else 0.0, 0.0, 0)[0]
+        for name, ids in (("every k-th", strided), ("rt_accum_select", selected)):
+            n = int(ids.size)
+            if n == 0:
+                continue
+            ids_d[:n] = torch.from_numpy(ids.astype(np.int32)).to(dev)
+            torch.cuda.synchronize()
+            t_list, t_full = _timed_pair(listed(n), full, args.reps)
+            r_list, r_full = n * spp / t_list / 1e3, npix * spp / t_full / 1e3
+            log(f"{frac:7.2f}   {name:15s} {n:9d} {t_list:9.3f} {t_full:9.3f} {r_list:10.1f} {r_full:10.1f} "
+                f"{t_list / t_full:9.3f}")
+            rows.append((n / npix, t_list, t_full, name))
+            if frac == 1.0 and name == "every k-th":
+                rate100 = r_list / r_full
+    log(f"100 % list rate over the full-frame megakernel's: {rate100:.3f}")
+    # break-even: the fraction at which the list's time reaches the full frame's (linear between measured points)
+    for name in ("every k-th", "rt_accum_select"):
+        pts = sorted((f, tl / tf) for f, tl, tf, nm in rows if nm == name)
+        be = None
+        for (f0, r0), (f1, r1) in zip(pts, pts[1:]):
+            if r0 < 1.0 <= r1:
+                be = f0 + (1.0 - r0) * (f1 - f0) / (r1 - r0)
+        log(f"break-even fraction ({name}): " + (f"{be:.2f}" if be is not None else
+                                                 "none below 100 % (a sparse pass never costs more than a full pass)"
+                                                 if pts and pts[-1][1] < 1.0 else "below the smallest list measured"))
+    # the selection and the sparse merge
+    n_out = ctypes.c_int64()
+
+    def select():
+        rt_amd._check(rt_amd.lib.rt_accum_select_device(acc.handle, 0.04, 0.0, 0, V(ids_d.data_ptr()), npix,
+                                                        ctypes.byref(n_out), st))
+
+    half = np.arange(0, npix, 2, dtype=np.uint32)
+    ids_h = torch.from_numpy(half.astype(np.int32)).to(dev)
+
+    def merge():
+        rt_amd._check(rt_amd.lib.rt_accum_add_sub_pixels_device(acc.handle, V(ids_h.data_ptr()), half.size,
+                                                                V(lsub.data_ptr()), 4, st))
+
+    t_sel, t_merge = _timed_pair(select, merge, args.reps)
+    log(f"rt_accum_select_device (resolve of the variance + 3 kernels + the count's read-back): {t_sel:.3f} ms")
+    log(f"rt_accum_add_sub_pixels_device, 50 % list: {t_merge:.3f} ms "
+        f"({half.size * 500 / t_merge / 1e6:.0f} GB/s of its minimum traffic: 500 B per entry, the pass 96, S and Q "
+        "read and written 384, the counts 16, the id 4)")
+    acc.close()
+
+
+def cmd_target(args):
+    if rt_amd.device_count() < 1:
+        raise RuntimeError("adapt_probe: no HIP device visible (it measures on the GPU only)")
+    log = Log(args.log)
+    w, h = _size(args.size)
+    seed = 77
+    log(f"# adapt_probe target: {w}x{h}, two 8-spp passes + up to 30 sparse passes of 16 spp, seeds pass_seed({seed}, k); "
+        "uniform: pass_seed(1077, k); truth: 4096 spp, seed 999")
+    log("scene            abs_tol  mean spp  max spp  mean/max  passes  RMSE adaptive  RMSE uniform (spp)  ratio")
+    for name in SCENES:
+        sc = _scene(name)
+        _, tsub, _ = rt_amd.render(sc, w, h, 4096, 999, megakernel=True, want_sub=True)
+        truth = _c_of(tsub)
+        for abs_tol in (0.03, 0.04, 0.06):
+            with rt_amd.Accumulator(w, h) as acc:
+                acc.add(sc, 8, rt_amd.pass_seed(seed, 0))
+                acc.add(sc, 8, rt_amd.pass_seed(seed, 1))
+                passes = 0
+                for k in range(2, 32):
+                    ids, n = acc.select(abs_tol, 0.0, 0)
+                    if n == 0:
+                        break
+                    acc.add_pixels(sc, ids, 16, rt_amd.pass_seed(seed, k))
+                    passes += 1
+                n_p = acc.counts()[1].astype(np.float64)
+                rmse_a = float(np.sqrt(np.mean((_c_of(acc.resolve()[0]) - truth) ** 2)))
+            mean_spp, max_spp = 4 * n_p.mean(), 4 * n_p.max()
+            with rt_amd.Accumulator(w, h) as uni:
+                k, spp = 0, 0
+                while spp < mean_spp:
+                    size = 8 if k < 2 else 16
+                    uni.add(sc, size, rt_amd.pass_seed(seed + 1000, k))
+                    spp += size
+                    k += 1
+                rmse_u = float(np.sqrt(np.mean((_c_of(uni.resolve()[0]) - truth) ** 2)))
+            log(f"{name:16s} {abs_tol:7.2f} {mean_spp:9.1f} {max_spp:8.0f} {mean_spp / max_spp:9.3f} {passes:7d} "
+                f"{rmse_a:14.5f} {rmse_u:13.5f} ({spp:3d}) {rmse_a / rmse_u:6.3f}")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    sp = ap.add_subparsers(dest="cmd", required=True)
+    t = sp.add_parser("time")
+    t.add_argument("--size", default="1920x1080")
+    t.add_argument("--reps", type=int, default=30)
+    t.add_argument("--log", default=os.path.join(REPO, "profiles", "adapt_time.log"))
+    t.set_defaults(fn=cmd_time)
+    g = sp.add_parser("target")
+    g.add_argument("--size", default="96x72")
+    g.add_argument("--log", default=os.path.join(REPO, "profiles", "adapt_target.log"))
+    g.set_defaults(fn=cmd_target)
+    args = ap.parse_args()
+    args.fn(args)
+
+
+if __name__ == "__main__":
+    main()
