@@ -274,6 +274,19 @@ extern "C" {
         stream: *mut c_void,
     ) -> c_int;
 
+    /// Camera views and accumulator reprojection (rt_ffi.h). `view`: an `RtView`, the 10 doubles of
+    /// an `rt_view`. The new handle shares `base`'s data (no device call, no copy) and has its own camera; `base`
+    /// must outlive it; `rt_scene_destroy` releases it.
+    pub fn rt_scene_view(base: *const RtScene, view: *const f64 /* [10] */, out: *mut *mut RtScene) -> c_int;
+    /// The camera of a scene or view, as an `RtView`.
+    pub fn rt_scene_get_view(scene: *const RtScene, view_out: *mut f64 /* [10] */) -> c_int;
+    /// Seeds accumulator `dst` (view `dst_view`) from `src` (view `src_view`): `max_n` >= 1 caps the inherited
+    /// samples per subpixel; `n_valid` (nullable): dst pixels that received history.
+    pub fn rt_accum_reproject(
+        dst: *mut c_void, src: *mut c_void, dst_view: *const RtScene, src_view: *const RtScene, flags: u32,
+        max_n: i32, n_valid: *mut i64,
+    ) -> c_int;
+
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_abi_version() -> c_int;
     pub fn rt_device_count() -> c_int;
@@ -287,6 +300,22 @@ unsafe impl Sync for Scene {}
 impl Drop for Scene {
     fn drop(&mut self) {
         unsafe { rt_scene_destroy(self.0) }
+    }
+}
+
+/// `rt_view` as the ABI passes it: pos[3], dir[3], right[3], fov (the reference's camera is
+/// right = (1, 0, 0), fov = 0.5135, src/server.rs:328-331).
+pub type RtView = [f64; 10];
+
+/// A handle on `base`'s scene data with its own camera (`rt_scene_view`). The caller keeps `base` alive for as long
+/// as the view lives.
+pub fn scene_view(base: &Scene, view: &RtView) -> Result<Scene, String> {
+    let mut s: *mut RtScene = std::ptr::null_mut();
+    let rc = unsafe { rt_scene_view(base.0, view.as_ptr(), &mut s) };
+    if rc == RT_OK {
+        Ok(Scene(s))
+    } else {
+        Err(format!("rt_scene_view: {} ({})", rc, last_error()))
     }
 }
 

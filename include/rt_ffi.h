@@ -18,6 +18,8 @@
  *                          a filter guided by it)
  *   rt_render_pixels, rt_accum_select, rt_accum_add_pixels: no counterpart either (rendering to a per-pixel error
  *                          target with sparse pixel-list passes)
+ *   rt_scene_view, rt_accum_reproject: no counterpart either (camera views of one scene, and an accumulator's
+ *                          history carried across a camera move)
  *
  * Conventions (mirroring the reference's):
  *   - a scene is immutable after creation and may be shared by concurrent rt_render calls
@@ -46,7 +48,8 @@ extern "C" {
                              (rt_render_features*, rt_denoise*) are additive: no struct or existing call changed, so
                              the version stays 3; likewise progressive accumulation (rt_accum_*, rt_denoise_var*) and
                              the error-target calls (rt_render_pixels*, rt_accum_add_pixels, rt_accum_add_sub_pixels*,
-                             rt_accum_counts, rt_accum_select*) */
+                             rt_accum_counts, rt_accum_select*) and the views and reprojection (rt_scene_view,
+                             rt_scene_get_view, rt_accum_reproject) */
 
 /* return codes */
 #define RT_OK 0
@@ -335,6 +338,58 @@ int rt_accum_select(void* accum, float abs_tol, float rel_tol, int32_t max_n, ui
  * and then writes *n_out on the host. */
 int rt_accum_select_device(void* accum, float abs_tol, float rel_tol, int32_t max_n, void* d_pixels, int64_t cap,
                            int64_t* n_out, void* stream);
+
+/* Camera views and accumulator reprojection ---------------------------------------- */
+/* A camera: position, viewing direction, the image's right-hand direction and the vertical field factor of
+ * server.rs:330 (0.5135 there). On the wire a view is its 10 doubles in this order (pos, dir, right, fov): the calls
+ * below take `const double view[10]`, which is what a `const rt_view*` points to (no padding; cast it). */
+typedef struct { double pos[3], dir[3], right[3]; double fov; } rt_view;
+/* A scene handle that shares base's host data, packed tables, device uploads and workspace pool, with its own camera.
+ * No device call, no copy of the geometry. A view of a view refers to the root base. The base must outlive its views
+ * (the caller's contract); rt_scene_destroy releases a view without touching shared data. Every entry point that takes
+ * an rt_scene* accepts a view and behaves as if the base had been created with that camera (rt_scene_info and
+ * rt_scene_mesh answer for the base). Camera frame, with w, h the image size as doubles (server.rs:328-331 at
+ * right = (1, 0, 0), fov = 0.5135, bit for bit):
+ *   s = w * fov / h;   cx = right * s per component;   cy = norm(cross(cx, dir)) * fov
+ * dir and right are used as given (right's length scales the horizontal field). RT_E_INVAL, without a GPU, for a null
+ * argument, a non-finite component, fov <= 0, or cross(right, dir) zero or not finite. */
+int rt_scene_view(const rt_scene* base, const double view[10], rt_scene** out);
+/* The camera of a scene or view; a loaded / created scene reports right = (1, 0, 0), fov = 0.5135. */
+int rt_scene_get_view(const rt_scene* scene, double view_out[10]);
+
+/* Seeds accumulator dst (view dst_view) from accumulator src (view src_view) of the same width, height and device.
+ * flags: 0 or RT_FLAG_MESH_NEAREST. max_n >= 1: the most samples per subpixel of history a pixel may inherit.
+ * *n_valid (nullable): dst pixels that received history. RT_E_INVAL, before any device call, for a null handle,
+ * dst == src, different size or device, views that do not share a base, src with K < 2, max_n < 1, an unknown flag.
+ * Arithmetic: f64 without FMA contraction, so that numpy gives the same bits. With
+ *   cross(a, b) = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x),  dot(a, b) = (a_x b_x + a_y b_y) + a_z b_z,
+ * pos_s, dir_s the src view's camera and cx_s, cy_s its frame at this width and height, the host computes
+ *   D = dot(cx_s, cross(cy_s, dir_s))
+ *   A = cross(cy_s, dir_s) / D,   B = cross(dir_s, cx_s) / D,   C = cross(cx_s, cy_s) / D     (per component)
+ * For dst pixel p (id = row * width + col, row 0 = top) and subpixel j = 2 sy + sx (rt_render's order):
+ *  1. the dst view's camera ray through the tent filter's centre (rt_render_features' ray) is traced like
+ *     rt_trace_rays_flags(flags); a miss is invalid;
+ *  2. the hit object's BRDF must be RT_BRDF_DIFFUSE (emission allowed), anything else is invalid; x, n = the hit
+ *     position and normal as rt_trace_rays reports them (n faces the dst camera);
+ *  3. v = x - pos_s;  al = dot(v, A), be = dot(v, B), ga = dot(v, C); invalid unless ga > 0;
+ *  4. fx = (al / ga + 0.5) * w,  fy = (be / ga + 0.5) * h; invalid unless 0 <= fx < w and 0 <= fy < h (NaN fails);
+ *     col' = floor(fx), sx' = floor((fx - col') * 2), yref = floor(fy), sy' = floor((fy - yref) * 2),
+ *     row' = height - 1 - yref; the source is subpixel j' = 2 sy' + sx' of pixel q = row' * width + col' (nearest
+ *     subpixel, no interpolation);
+ *  5. invalid unless dot(n, pos_s - x) > 0 (the src camera is on the side the dst camera sees);
+ *  6. invalid unless Scene::mutually_visible(x, pos_s) (scene.rs:258-270, the shadow query of rt_render).
+ * The pixel is valid iff its four subpixels are. With (K_q, N_q) the src counts of each subpixel's source pixel
+ * (rt_accum_counts of src), all integers 64-bit:
+ *   N_p = min(max_n, min_j N_qj)        K_p = max(2, min_j ceil(K_qj * N_p / N_qj))
+ *   S_dst[p][j][c] = (double)N_p * (S_src[q_j][j'][c] / (double)N_qj),  Q_dst likewise from Q_src,  counts (K_p, N_p)
+ * (dividing first keeps the subpixel mean and Q / N - m m; K scales with N: the shortened history counts as fewer
+ * passes of the same size). An invalid pixel gets zeros in all 24 sums and counts (0, 0); every dst entry is written.
+ * Afterwards dst is reset and seeded: its per-pixel counts are live, rt_accum_info reports K = N = 0 (the full-frame
+ * passes since the reprojection), and the next merge adds to the seeded sums instead of storing. rt_accum_reset
+ * clears the seeded state. rt_accum_resolve keeps its K >= 1 rule and the variance its K >= 2 rule: after two
+ * full-frame passes every K_p >= 2, so rt_accum_select and the sparse merges work unchanged. src is only read. */
+int rt_accum_reproject(void* dst, void* src, const rt_scene* dst_view, const rt_scene* src_view, uint32_t flags,
+                       int32_t max_n, int64_t* n_valid);
 
 const char* rt_last_error(void);
 int rt_abi_version(void);

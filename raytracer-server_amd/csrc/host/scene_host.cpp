@@ -455,10 +455,12 @@ int pick_light(Scene* s, std::string* err) {
     return RT_OK;
 }
 
-void camera_frame(const Scene& s, int width, int height, double cx[3], double cy[3]) {
+void camera_frame(const double dir[3], const double right[3], double fov, int width, int height, double cx[3],
+                  double cy[3]) {
     double w = (double)width, h = (double)height;
-    D3 x{w * 0.5135 / h, 0., 0.};
-    D3 y = scale(normd(crossp(x, s.cam_dir)), 0.5135);
+    const double s = w * fov / h;
+    D3 x{right[0] * s, right[1] * s, right[2] * s};  // right = (1, 0, 0): (s, 0, 0), the reference's cx
+    D3 y = scale(normd(crossp(x, D3{dir[0], dir[1], dir[2]})), fov);
     cx[0] = x.x; cx[1] = x.y; cx[2] = x.z;
     cy[0] = y.x; cy[1] = y.y; cy[2] = y.z;
 }

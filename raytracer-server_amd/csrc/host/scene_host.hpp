@@ -78,7 +78,9 @@ Mesh make_mesh(std::vector<D3> vertices, std::vector<uint32_t> indices);
 void build_octree(Mesh& m);
 // scene.rs:126-141 — light = first object whose emission is not within 1e-5 of zero.
 int pick_light(Scene* s, std::string* err);
-// camera frame of sample_pixel (server.rs:328-331)
-void camera_frame(const Scene& s, int width, int height, double cx[3], double cy[3]);
+// camera frame of sample_pixel (server.rs:328-331) for a view (rt_ffi.h rt_view): s = w * fov / h, cx = right * s,
+// cy = norm(cross(cx, dir)) * fov; the reference's frame, bit for bit, at right = (1, 0, 0), fov = 0.5135
+void camera_frame(const double dir[3], const double right[3], double fov, int width, int height, double cx[3],
+                  double cy[3]);
 
 }  // namespace rt::host

@@ -21,6 +21,7 @@
 #include "kernels/accum.h"
 #include "kernels/denoise.h"
 #include "kernels/kernels.h"
+#include "kernels/reproject.h"
 #include "kernels/wavefront.h"
 
 #ifndef RT_LTRI_INDEX
@@ -102,17 +103,37 @@ struct DeviceCopy {
 
 }  // namespace
 
-struct rt_scene {
+// What a loaded or created scene owns and its views share: host data, packed tables, device uploads, workspaces.
+struct SceneData {
     rt::host::Scene host;
     Packed packed;
     std::mutex mu;
     std::vector<DeviceCopy> dev;
     std::vector<std::unique_ptr<rt::Workspace>> pool;  // free wavefront workspaces, per device tagged
-    ~rt_scene() {
+    ~SceneData() {
         for (auto& d : dev)
             if (d.blob) (void)hipFree(d.blob);
         pool.clear();
     }
+};
+
+// A scene handle: the data (its own, or for a view, rt_scene_view, the root base's) and a camera. The members below
+// refer to the root's data, so every entry point reads a view as it reads a scene; only the camera is the handle's.
+struct rt_scene {
+    std::unique_ptr<SceneData> own;  // null in a view
+    const rt_scene* root;            // the handle that owns the data (this, unless a view)
+    rt::host::Scene& host;
+    Packed& packed;
+    std::mutex& mu;
+    std::vector<DeviceCopy>& dev;
+    std::vector<std::unique_ptr<rt::Workspace>>& pool;
+    double cam_pos[3] = {0, 0, 0}, cam_dir[3] = {0, 0, 1}, cam_right[3] = {1, 0, 0};
+    double cam_fov = 0.5135;  // server.rs:330
+    rt_scene()
+        : own(new SceneData), root(this), host(own->host), packed(own->packed), mu(own->mu), dev(own->dev),
+          pool(own->pool) {}
+    explicit rt_scene(const rt_scene* base)  // a view of base (of base's root, when base is a view itself)
+        : root(base->root), host(base->host), packed(base->packed), mu(base->mu), dev(base->dev), pool(base->pool) {}
 };
 
 namespace {
@@ -778,13 +799,14 @@ int upload(rt_scene* s, int device, rt::DevScene* out) {
             else if (L.geom == rt::GEOM_MESH) ds.light_pdf = 1. / p.meshes[L.mesh].surface_area;  // :591
         }
         ds.n_meshes = (int32_t)p.meshes.size();
-        cp3(ds.cam_pos, s->host.cam_pos);
-        cp3(ds.cam_dir, s->host.cam_dir);
         dc.blob = d;
         dc.ds = ds;
         dc.ready = true;
     }
     *out = dc.ds;
+    // the camera is the handle's own (a view shares everything else): the kernels read it from this kernarg copy
+    std::memcpy(out->cam_pos, s->cam_pos, sizeof out->cam_pos);
+    std::memcpy(out->cam_dir, s->cam_dir, sizeof out->cam_dir);
     return RT_OK;
 }
 
@@ -1015,7 +1037,7 @@ rt::RenderArgs make_render_args(const rt_scene* s, const rt_render_params* p, co
         for (const auto& dm : s->packed.meshes) a.all_flat &= dm.flat != 0;
     }
     a.seed = p->seed;
-    rt::host::camera_frame(s->host, p->width, p->height, a.cx, a.cy);
+    rt::host::camera_frame(s->cam_dir, s->cam_right, s->cam_fov, p->width, p->height, a.cx, a.cy);
     a.inv_n = a.n_samples > 0 ? 1. / (double)a.n_samples : 0.0;
     return a;
 }
@@ -1136,9 +1158,40 @@ int rt_device_count(void) {
 static int finish_scene(rt::host::Scene&& sc, rt_scene** out) {
     auto s = std::make_unique<rt_scene>();
     s->host = std::move(sc);
+    cp3(s->cam_pos, s->host.cam_pos);
+    cp3(s->cam_dir, s->host.cam_dir);
     const int rc = pack_scene(s.get());
     if (rc != RT_OK) return rc;
     *out = s.release();
+    return RT_OK;
+}
+
+int rt_scene_view(const rt_scene* base, const double view[10], rt_scene** out) {
+    if (out) *out = nullptr;
+    if (!base || !view || !out) return fail(RT_E_INVAL, "rt_scene_view: null argument");
+    for (int k = 0; k < 10; ++k)
+        if (!std::isfinite(view[k])) return fail(RT_E_INVAL, "rt_scene_view: every component must be finite");
+    const double *dir = view + 3, *right = view + 6, fov = view[9];
+    if (!(fov > 0.0)) return fail(RT_E_INVAL, "rt_scene_view: fov must be > 0");
+    const double c[3] = {right[1] * dir[2] - right[2] * dir[1], right[2] * dir[0] - right[0] * dir[2],
+                         right[0] * dir[1] - right[1] * dir[0]};
+    if (!std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]) || (c[0] == 0.0 && c[1] == 0.0 && c[2] == 0.0))
+        return fail(RT_E_INVAL, "rt_scene_view: cross(right, dir) must be finite and not zero");
+    rt_scene* v = new rt_scene(base);
+    std::memcpy(v->cam_pos, view, 3 * sizeof(double));
+    std::memcpy(v->cam_dir, dir, 3 * sizeof(double));
+    std::memcpy(v->cam_right, right, 3 * sizeof(double));
+    v->cam_fov = fov;
+    *out = v;
+    return RT_OK;
+}
+
+int rt_scene_get_view(const rt_scene* scene, double view_out[10]) {
+    if (!scene || !view_out) return fail(RT_E_INVAL, "rt_scene_get_view: null argument");
+    std::memcpy(view_out, scene->cam_pos, 3 * sizeof(double));
+    std::memcpy(view_out + 3, scene->cam_dir, 3 * sizeof(double));
+    std::memcpy(view_out + 6, scene->cam_right, 3 * sizeof(double));
+    view_out[9] = scene->cam_fov;
     return RT_OK;
 }
 
@@ -1510,7 +1563,7 @@ int features_enqueue(rt_scene* s, const rt_render_params* p, float* d_feat, hipS
     a.th = p->tile_h;
     a.row_step = p->row_step > 1 ? p->row_step : 1;
     a.nearest = (p->flags & RT_FLAG_MESH_NEAREST) && !s->host.meshes.empty();
-    rt::host::camera_frame(s->host, p->width, p->height, a.cx, a.cy);
+    rt::host::camera_frame(s->cam_dir, s->cam_right, s->cam_fov, p->width, p->height, a.cx, a.cy);
     HIP_TRY(rt::launch_features_f64(ds, a, d_feat, st));
     return RT_OK;
 }
@@ -1687,6 +1740,9 @@ struct rt_accum {
     // the first sparse merge or selection; they are valid (and used) once a sparse pass has been merged
     char* adapt = nullptr;
     bool sparse = false;
+    // seeded by rt_accum_reproject: S, Q and the per-pixel counts hold reprojected history although
+    // no full-frame pass has been merged since (K = N = 0), so the next merge adds instead of storing
+    bool seeded = false;
     uint32_t* cnt() const { return (uint32_t*)adapt; }
     size_t npix() const { return (size_t)width * height; }
     size_t sub_bytes() const { return npix() * 12 * sizeof(double); }
@@ -1734,7 +1790,7 @@ int accum_ready(rt_accum* a, bool sums, bool stage) {
 
 // Merges the pass in d_sub on `st`, waits for it and counts it.
 int accum_merge(rt_accum* a, const double* d_sub, int32_t n, hipStream_t st) {
-    hipError_t e = rt::launch_accum_add(a->S, a->Q, d_sub, (long)a->npix(), n, a->K == 0, st);
+    hipError_t e = rt::launch_accum_add(a->S, a->Q, d_sub, (long)a->npix(), n, a->K == 0 && !a->seeded, st);
     if (e == hipSuccess && a->sparse) e = rt::launch_accum_cnt_fill(a->cnt(), (long)a->npix(), 1u, (uint32_t)n, true, st);
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
@@ -1845,6 +1901,7 @@ int rt_accum_reset(void* accum) {
     a->K = 0;  // the next pass stores without reading
     a->N = 0;
     a->sparse = false;  // the per-pixel counts are forgotten with the passes
+    a->seeded = false;  // and so is reprojected history
     return RT_OK;
 }
 
@@ -2377,6 +2434,85 @@ int rt_accum_select(void* accum, float abs_tol, float rel_tol, int32_t max_n, ui
     if (rc != RT_OK) return rc;
     const int64_t n = std::min(*n_out, dcap);
     if (n > 0) HIP_TRY(hipMemcpy(pixels_out, adapt_list(a), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// Accumulator reprojection across camera moves ---------------------------------------------
+
+int rt_accum_reproject(void* dst, void* src, const rt_scene* dst_view, const rt_scene* src_view, uint32_t flags,
+                       int32_t max_n, int64_t* n_valid) {
+    rt_accum* d = (rt_accum*)dst;
+    const rt_accum* s = (const rt_accum*)src;
+    if (!d || !s || !dst_view || !src_view) return fail(RT_E_INVAL, "rt_accum_reproject: null argument");
+    if (d == s) return fail(RT_E_INVAL, "rt_accum_reproject: dst and src must be two accumulators");
+    if (d->width != s->width || d->height != s->height || d->device != s->device)
+        return fail(RT_E_INVAL, "rt_accum_reproject: dst and src differ in size or device");
+    if (dst_view->root != src_view->root) return fail(RT_E_INVAL, "rt_accum_reproject: the two views do not share a base");
+    if (max_n < 1) return fail(RT_E_INVAL, "rt_accum_reproject: max_n must be >= 1");
+    if (flags & ~RT_FLAG_MESH_NEAREST) return fail(RT_E_INVAL, "rt_accum_reproject: unknown flag");
+    if (s->K < 2) return fail(RT_E_INVAL, "rt_accum_reproject: src needs at least two full-frame passes");
+    int rc = need_device("rt_accum_reproject", d->device);
+    if (rc == RT_OK) rc = accum_ready(d, true, false);
+    if (rc == RT_OK) rc = adapt_ready(d);
+    if (rc != RT_OK) return rc;
+    rt::DevScene ds;
+    rc = upload(const_cast<rt_scene*>(dst_view), d->device, &ds);  // the dst view's camera rides in ds
+    if (rc != RT_OK) return rc;
+    rt::ReprojArgs a{};
+    a.width = d->width;
+    a.height = d->height;
+    a.nearest = (flags & RT_FLAG_MESH_NEAREST) && !dst_view->host.meshes.empty();
+    a.max_n = max_n;
+    rt::host::camera_frame(dst_view->cam_dir, dst_view->cam_right, dst_view->cam_fov, d->width, d->height, a.cx, a.cy);
+    {
+        // the inverse of (cx_s | cy_s | dir_s) by cofactors (rt_ffi.h): cross(a, b) = (a_y b_z - a_z b_y, a_z b_x -
+        // a_x b_z, a_x b_y - a_y b_x), dot = (a_x b_x + a_y b_y) + a_z b_z, no FMA contraction
+        double cxs[3], cys[3];
+        const double* dir = src_view->cam_dir;
+        rt::host::camera_frame(dir, src_view->cam_right, src_view->cam_fov, d->width, d->height, cxs, cys);
+        auto cross = [](const double* u, const double* v, double* o) {
+            o[0] = u[1] * v[2] - u[2] * v[1];
+            o[1] = u[2] * v[0] - u[0] * v[2];
+            o[2] = u[0] * v[1] - u[1] * v[0];
+        };
+        double yd[3], dx[3], xy[3];
+        cross(cys, dir, yd);
+        cross(dir, cxs, dx);
+        cross(cxs, cys, xy);
+        const double D = cxs[0] * yd[0] + cxs[1] * yd[1] + cxs[2] * yd[2];
+        for (int k = 0; k < 3; ++k) {
+            a.A[k] = yd[k] / D;
+            a.B[k] = dx[k] / D;
+            a.C[k] = xy[k] / D;
+            a.pos_s[k] = src_view->cam_pos[k];
+        }
+    }
+    a.S_src = s->S;
+    a.Q_src = s->Q;
+    a.cnt_src = s->sparse ? s->cnt() : nullptr;
+    a.K_src = (uint32_t)s->K;
+    a.N_src = (uint32_t)s->N;
+    a.S_dst = d->S;
+    a.Q_dst = d->Q;
+    a.cnt_dst = d->cnt();
+    a.n_valid = (unsigned long long*)adapt_total(d);
+    // dst is reset first: whatever happens below, it never keeps half of an earlier history
+    d->K = 0;
+    d->N = 0;
+    d->sparse = false;
+    d->seeded = false;
+    CallStream cs;
+    HIP_TRY(cs.init());
+    unsigned long long count = 0;
+    hipError_t e = hipMemsetAsync(a.n_valid, 0, sizeof(unsigned long long), cs.st);
+    if (e == hipSuccess) e = rt::launch_reproject_f64(ds, a, cs.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&count, a.n_valid, sizeof count, hipMemcpyDeviceToHost, cs.st);
+    const hipError_t es = hipStreamSynchronize(cs.st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_reproject: ") + hipGetErrorString(e));
+    d->sparse = true;  // the per-pixel counts are live
+    d->seeded = true;  // the next merge adds
+    if (n_valid) *n_valid = (int64_t)count;
     return RT_OK;
 }
 

@@ -10,6 +10,8 @@ Beyond the reference: render_features / denoise / render_denoised, denoised prev
 (rt_render_features, rt_denoise). Accumulator / denoise_var / render_progressive: progressive refinement
 (rt_accum_*, rt_denoise_var). render_pixels / Accumulator.select / add_pixels / render_to_error: rendering
 to a per-pixel error target with sparse pixel-list passes (rt_render_pixels, rt_accum_select).
+Scene.view / Scene.camera / look_at / Accumulator.reproject_from / render_interactive: camera views of one scene and
+an accumulator's history carried across a camera move (rt_scene_view, rt_accum_reproject).
 
 Everything computes on the GPU through lib/librtamd.so; there is no CPU fallback. Importing this
 module without the built library raises ImportError.
@@ -75,6 +77,11 @@ class SceneDesc(ctypes.Structure):
                 ("meshes", ctypes.POINTER(MeshDesc))]
 
 
+class View(ctypes.Structure):
+    """rt_view: the 10 doubles rt_scene_view / rt_scene_get_view take."""
+    _fields_ = [("pos", _D3), ("dir", _D3), ("right", _D3), ("fov", ctypes.c_double)]
+
+
 _EXPORTS = ["rt_scene_load_toml", "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_mesh",
             "rt_render", "rt_render_device", "rt_render_multi", "rt_band_plan", "rt_trace_rays", "rt_trace_rays_flags", "rt_last_error", "rt_abi_version",
             "rt_device_count", "rt_render_features", "rt_render_features_device", "rt_denoise", "rt_denoise_device",
@@ -82,7 +89,7 @@ _EXPORTS = ["rt_scene_load_toml", "rt_scene_create", "rt_scene_destroy", "rt_sce
             "rt_accum_add_sub_device", "rt_accum_resolve", "rt_accum_resolve_device", "rt_denoise_var",
             "rt_denoise_var_device", "rt_render_pixels", "rt_render_pixels_device", "rt_accum_add_pixels",
             "rt_accum_add_sub_pixels", "rt_accum_add_sub_pixels_device", "rt_accum_counts", "rt_accum_select",
-            "rt_accum_select_device"]
+            "rt_accum_select_device", "rt_scene_view", "rt_scene_get_view", "rt_accum_reproject"]
 
 
 def _load():
@@ -138,6 +145,9 @@ def _load():
     L.rt_accum_counts.argtypes = [vp, P(U32), P(U32)]
     L.rt_accum_select.argtypes = [vp, F, F, I, P(U32), I64, P(I64)]
     L.rt_accum_select_device.argtypes = [vp, F, F, I, vp, I64, P(I64), vp]
+    L.rt_scene_view.argtypes = [vp, P(View), P(vp)]
+    L.rt_scene_get_view.argtypes = [vp, P(View)]
+    L.rt_accum_reproject.argtypes = [vp, vp, vp, vp, U32, I, P(I64)]
     L.rt_last_error.restype = ctypes.c_char_p
     L.rt_last_error.argtypes = []
     L.rt_abi_version.argtypes = []
@@ -189,8 +199,27 @@ def _ptr(a, ct):
 class Scene:
     """Immutable scene (SceneSpec::to_scene, scene.rs:357). Share it freely across renders."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, base=None):
         self._h = ctypes.c_void_p(handle)
+        self._base = base  # a view keeps the scene whose data it shares alive
+
+    def view(self, pos, dir, right=(1.0, 0.0, 0.0), fov=0.5135):
+        """A Scene that shares this one's data (host tables, device uploads, workspaces: no copy, no device call) with
+        its own camera (rt_scene_view). Every call that takes a scene takes a view. right = (1, 0, 0), fov = 0.5135
+        is the reference's camera frame; right's length scales the horizontal field."""
+        v = View()
+        for j in range(3):
+            v.pos[j], v.dir[j], v.right[j] = pos[j], dir[j], right[j]
+        v.fov = fov
+        h = ctypes.c_void_p()
+        _check(lib.rt_scene_view(self._h, ctypes.byref(v), ctypes.byref(h)))
+        return Scene(h.value, base=self._base if self._base is not None else self)
+
+    def camera(self):
+        """The camera of this scene or view: dict(pos, dir, right, fov) (rt_scene_get_view)."""
+        v = View()
+        _check(lib.rt_scene_get_view(self._h, ctypes.byref(v)))
+        return dict(pos=tuple(v.pos), dir=tuple(v.dir), right=tuple(v.right), fov=v.fov)
 
     @classmethod
     def from_toml(cls, path, assets_dir=None):
@@ -547,6 +576,30 @@ class Accumulator:
         _check(lib.rt_accum_add_sub_pixels(self._h, _ptr(px, ctypes.c_uint32), px.size, _ptr(sub, ctypes.c_double), n))
 
 
+    def reproject_from(self, src, dst_scene, src_scene, max_n, mesh_nearest=False):
+        """Seeds this accumulator (its frame seen from dst_scene) from accumulator `src` (seen from src_scene, a view
+        of the same base): every pixel whose four tent-centre first hits are diffuse, project into src's frame and are
+        visible from src's camera inherits the nearest src subpixels' history, at most max_n samples per subpixel
+        (rt_accum_reproject). Whatever this accumulator held is dropped. Returns the number of pixels
+        that received history; info() then counts the full-frame passes since the reprojection."""
+        n = ctypes.c_int64(0)
+        _check(lib.rt_accum_reproject(self._h, src.handle, dst_scene.handle, src_scene.handle,
+                                      FLAG_MESH_NEAREST if mesh_nearest else 0, max_n, ctypes.byref(n)))
+        return n.value
+
+
+def look_at(pos, target, up=(0.0, 1.0, 0.0), fov=0.5135):
+    """The arguments of Scene.view for a camera at pos looking at target: dict(pos, dir, right, fov) with
+    dir = norm(target - pos) and right = norm(cross(dir, up)), both unit length. For the shipped scenes' camera
+    (looking down -z, up = +y) right is the reference's (1, 0, 0)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    d = np.asarray(target, dtype=np.float64) - pos
+    d = d / np.sqrt(d.dot(d))
+    r = np.cross(d, np.asarray(up, dtype=np.float64))
+    r = r / np.sqrt(r.dot(r))
+    return dict(pos=tuple(pos.tolist()), dir=tuple(d.tolist()), right=tuple(r.tolist()), fov=fov)
+
+
 def render_pixels(scene, width, height, pixels, spp, seed=0x5EED, mis=False, device=0, want_sub=False, want_rgb=True,
                   cancel=None):
     """Renders only the listed pixels of the width x height frame (rt_render_pixels): pixels are strictly ascending ids
@@ -677,6 +730,66 @@ def render_to_error(scene, width, height, abs_tol=None, max_spp=512, first=None,
             if acc.add_pixels(scene, ids, pass_spp, pass_seed(seed, k), cancel=cancel)["cancelled"]:
                 return
             k += 1
+
+
+# Orbiting a scene ---------------------------------------------------------------------------
+
+def render_interactive(scene, views, width, height, first=8, max_n=64, abs_tol=None, rel_tol=0.0, view_spp=0,
+                       pass_spp=16, seed=0x5EED, device=0, cancel=None, **denoise_params):
+    """A generator over camera views of one scene that carries the accumulated samples across the camera moves. views:
+    an iterable (read lazily, one view per frame) of Scene.view keyword dicts (look_at makes them; a "view_spp" key
+    overrides the budget for that view) or Scene objects that are views of `scene`. For each view it
+      1. seeds an accumulator from the previous view's (Accumulator.reproject_from, at most max_n samples per subpixel
+         of history; two accumulators take turns),
+      2. merges two full-frame passes of `first` spp each, which give the pixels without history a variance,
+      3. with abs_tol set, spends sparse passes of pass_spp on the pixels Accumulator.select returns (their estimated
+         error above abs_tol + rel_tol * luminance / 3, fewer than max_n samples per subpixel) until none is left or
+         the view's samples reach view_spp per pixel on average,
+      4. resolves, computes the view's features and filters with denoise_var (denoise_params: levels / sigma_*),
+    and yields (rgb[h, w, 3] u8, fraction of pixels that received history, camera samples traced for this view). Pass k
+    of the whole sequence renders with pass_seed(seed, k): one counter over all views, so no pass repeats a seed the
+    history already holds. A raised cancel word ends the generator."""
+    half = max(4, first // 4 * 4)
+    pass_spp = max(4, pass_spp // 4 * 4)
+    npix = width * height
+    default_spp = view_spp
+    accs = [Accumulator(width, height, device), Accumulator(width, height, device)]
+    try:
+        prev_view, k = None, 0
+        for i, view in enumerate(views):
+            view_spp = default_spp
+            if isinstance(view, dict):  # a view dict may carry its own budget
+                view = dict(view)
+                view_spp = view.pop("view_spp", default_spp)
+            v = view if isinstance(view, Scene) else scene.view(**view)
+            acc, prev = accs[i & 1], accs[(i & 1) ^ 1]
+            n_valid = 0
+            if prev_view is not None:
+                n_valid = acc.reproject_from(prev, v, prev_view, max_n)
+            else:
+                acc.reset()
+            samples = 0
+            for _ in range(2):
+                if acc.add(v, half, pass_seed(seed, k), cancel=cancel)["cancelled"]:
+                    return
+                k += 1
+                samples += npix * half
+            while abs_tol is not None and samples + pass_spp <= view_spp * npix:
+                ids, _ = acc.select(abs_tol, rel_tol, max_n)
+                ids = ids[:(view_spp * npix - samples) // pass_spp]
+                if ids.size == 0:
+                    break
+                if acc.add_pixels(v, ids, pass_spp, pass_seed(seed, k), cancel=cancel)["cancelled"]:
+                    return
+                k += 1
+                samples += int(ids.size) * pass_spp
+            sub, var, _ = acc.resolve(want_var=True, want_rgb=False)
+            feat = render_features(v, width, height, device=device)
+            yield denoise_var(sub, feat, var, device=device, **denoise_params), n_valid / npix, samples
+            prev_view = v
+    finally:
+        for a in accs:
+            a.close()
 
 
 def band_plan(tile_h, n_workers, band_rows=0):

@@ -17,6 +17,12 @@ Run:  PORT=8080 python -m rt_amd.server <scenes dir>
       frame re-sent with the same chunk messages).
       RT_TARGET_ERROR=<abs_tol> selects jobs rendered to a per-pixel error target (rt_amd.render_to_error, DESIGN.md
       §13): RT_PROGRESSIVE gives the first frame's spp, the request's spp is the per-pixel budget.
+      RT_REPROJECT=<max_n> together with RT_PROGRESSIVE or RT_TARGET_ERROR: a connection keeps its last accumulator
+      and view, and a request for the same scene starts from the reprojected history (rt_amd.render_interactive,
+      DESIGN.md §14; at most max_n samples per subpixel are inherited).
+Beyond the reference's protocol the render message takes an optional camera, {"type": "render", ..., "camera":
+{"pos": [x, y, z], "dir": [x, y, z], "right": [x, y, z] (optional), "fov": f (optional)}}: the scene is rendered
+through Scene.view of it. Without it nothing changes; a bad camera is a logged error, like a bad scene name.
 """
 import asyncio
 import ctypes
@@ -42,6 +48,32 @@ def chunk_messages(rgb, y0):
         for x in range(0, width, PIXELS_PER_MSG):
             n = min(PIXELS_PER_MSG, width - x)
             yield struct.pack("<BBHH", 0, n, x, y0 + r) + rgb[r, x:x + n].tobytes()
+
+
+def parse_camera(m):
+    """The render message's optional "camera" as Scene.view's keyword arguments, or None without one. ValueError for
+    anything but {"pos": 3 numbers, "dir": 3 numbers[, "right": 3 numbers][, "fov": number]}."""
+    cam = m.get("camera")
+    if cam is None:
+        return None
+
+    def num(x):
+        return isinstance(x, (int, float)) and not isinstance(x, bool)
+
+    if not isinstance(cam, dict) or set(cam) - {"pos", "dir", "right", "fov"} or "pos" not in cam or "dir" not in cam:
+        raise ValueError(f"bad camera {cam!r}")
+    out = {}
+    for key in ("pos", "dir", "right"):
+        if key in cam:
+            v = cam[key]
+            if not isinstance(v, list) or len(v) != 3 or not all(num(x) for x in v):
+                raise ValueError(f"bad camera {key} {v!r}")
+            out[key] = tuple(float(x) for x in v)
+    if "fov" in cam:
+        if not num(cam["fov"]):
+            raise ValueError(f"bad camera fov {cam['fov']!r}")
+        out["fov"] = float(cam["fov"])
+    return out
 
 
 def gpu_band_renderer(device=0, fp32=False):
@@ -207,6 +239,72 @@ class AdaptiveJob:
             frames.close()
 
 
+class InteractiveJob:
+    """A whole-frame job whose connection keeps the last accumulator and view (rt_amd.render_interactive, DESIGN.md
+    §14): a request for the scene the connection rendered last starts from the history reprojected into the new
+    camera, at most max_n samples per subpixel of it; then two full-frame passes of `first` spp and, with abs_tol,
+    sparse passes up to the request's spp per pixel. One frame is sent per request. A request for another scene or
+    frame size starts over. RenderJob's interface; a stop ends the request and drops the history."""
+
+    def __init__(self, send, max_n, first=8, abs_tol=None, device=0, **denoise_params):
+        self.send = send
+        self.max_n = max_n
+        self.first = first
+        self.abs_tol = abs_tol
+        self.device = device
+        self.denoise_params = denoise_params
+        self.cancel = ctypes.c_int32(1)  # starts cancelled == not running
+        self._frames = None  # the running render_interactive generator and what it was made for
+        self._key = None
+        self._base = None
+        self._next_view = None
+
+    def running(self):
+        return self.cancel.value == 0
+
+    def stop(self):
+        self.cancel.value = 1
+
+    def _views(self):
+        while True:  # read by render_interactive when a frame is asked for
+            yield self._next_view
+
+    def _drop(self):
+        if self._frames is not None:
+            self._frames.close()
+        self._frames, self._key, self._base = None, None, None
+
+    async def run(self, scene, width, height, spp, seed):
+        """Returns True when stopped before the frame was sent."""
+        import rt_amd
+
+        self.cancel.value = 0
+        loop = asyncio.get_running_loop()
+        base = scene._base if scene._base is not None else scene
+        key = (id(base), width, height)
+        if self._frames is None or self._key != key:
+            self._drop()
+            self._frames = rt_amd.render_interactive(base, self._views(), width, height, first=self.first,
+                                                     max_n=self.max_n, abs_tol=self.abs_tol, seed=seed,
+                                                     device=self.device, cancel=self.cancel, **self.denoise_params)
+            self._key = key
+            self._base = base  # keeps id(base) unique while the generator lives
+        self._next_view = dict(scene.camera(), view_spp=spp)
+        frame = await loop.run_in_executor(None, next, self._frames, None)
+        if frame is None or self.cancel.value:
+            self._drop()  # a cancelled generator has ended: the next request starts over
+            self.cancel.value = 1
+            return True
+        for msg in chunk_messages(frame[0], 0):
+            try:
+                await self.send(msg)
+            except ConnectionError:
+                self.cancel.value = 1
+                return True
+        self.cancel.value = 1
+        return False
+
+
 class Server:
     def __init__(self, scenes, renderer=None, width=WIDTH, height=HEIGHT, band_rows=32, log=print, job_factory=None):
         self.scenes = scenes
@@ -252,10 +350,18 @@ class Server:
                     if name not in self.scenes or not isinstance(spp, int):
                         self.log(f"[{cid}] bad render request {m!r}")
                         continue
+                    scene = self.scenes[name]
+                    try:
+                        cam = parse_camera(m)
+                        if cam is not None:
+                            scene = scene.view(**cam)  # shares the scene's data; RtError for a degenerate camera
+                    except Exception as e:  # noqa: BLE001 (a bad camera is logged, like a bad scene name)
+                        self.log(f"[{cid}] bad render request {m!r}: {e}")
+                        continue
                     seed = int.from_bytes(os.urandom(8), "little") if "RT_SEED" not in os.environ \
                         else int(os.environ["RT_SEED"], 0)
                     self.log(f"[{cid}] Rendering...")
-                    task = asyncio.ensure_future(self._run(cid, job, self.scenes[name], spp, seed))
+                    task = asyncio.ensure_future(self._run(cid, job, scene, spp, seed))
                 elif kind == "stop_rendering" and job.running():
                     job.stop()
                     self.log(f"[{cid}] Render cancelled.")
@@ -299,7 +405,17 @@ def main(argv=None):
         # (geometry.rs:886-903), not the reference's first-hit octree walk (geometry.rs:1237-1295)
         print("RT_PRECISION=f32: f32 perf mode; meshes (flying_unicorn) use nearest-triangle hits, not the "
               "reference's octree semantics; frames differ statistically from server.rs", file=sys.stderr)
-    if "RT_TARGET_ERROR" in os.environ:
+    if "RT_REPROJECT" in os.environ and ("RT_TARGET_ERROR" in os.environ or "RT_PROGRESSIVE" in os.environ):
+        # orbiting: a connection keeps its accumulator and view; a new camera starts from the reprojected history
+        max_n = int(os.environ["RT_REPROJECT"])
+        abs_tol = float(os.environ["RT_TARGET_ERROR"]) if "RT_TARGET_ERROR" in os.environ else None
+        first = int(os.environ.get("RT_PROGRESSIVE", rt_amd.ERROR_TARGET_DEFAULTS["first"]))
+        print(f"RT_REPROJECT={max_n}: whole-frame jobs that inherit up to {max_n} samples per subpixel from the "
+              f"connection's last view; two passes of {first} spp per request"
+              + (f", then sparse passes to the error target {abs_tol} within the request's spp" if abs_tol is not None
+                 else ""), file=sys.stderr)
+        server = Server(scenes, job_factory=lambda send: InteractiveJob(send, max_n, first=first, abs_tol=abs_tol))
+    elif "RT_TARGET_ERROR" in os.environ:
         # rendering to an error target: whole frames, sparse passes over the pixels still above it
         abs_tol = float(os.environ["RT_TARGET_ERROR"])
         first = int(os.environ.get("RT_PROGRESSIVE", rt_amd.ERROR_TARGET_DEFAULTS["first"]))
