@@ -287,6 +287,25 @@ extern "C" {
         max_n: i32, n_valid: *mut i64,
     ) -> c_int;
 
+    /// Filling the holes of a reprojection (rt_ffi.h). The pixels of a seeded accumulator with
+    /// fewer than two passes, plus, with `period` > 0, those with `(col + 3 * row) % period == phase`; ascending,
+    /// at most `cap` written, `n_out` the full count, `n_holes` (nullable) the count with fewer than two passes.
+    pub fn rt_accum_holes(
+        accum: *mut c_void, period: i32, phase: i32, pixels_out: *mut u32, cap: i64, n_out: *mut i64,
+        n_holes: *mut i64,
+    ) -> c_int;
+    pub fn rt_accum_holes_device(
+        accum: *mut c_void, period: i32, phase: i32, d_pixels: *mut c_void, cap: i64, n_out: *mut i64,
+        n_holes: *mut i64, stream: *mut c_void,
+    ) -> c_int;
+    /// Two sparse passes (seeds `params.seed` and `seed2`) that give every hole two passes; afterwards the
+    /// accumulator is covered and resolves, selects and reprojects without a full-frame pass. `fill_out`
+    /// (nullable): the two lists' lengths. `RT_CANCELLED` leaves it uncovered; a later fill completes it.
+    pub fn rt_accum_fill(
+        accum: *mut c_void, scene: *const RtScene, params: *const RtRenderParams, seed2: u64, period: i32, phase: i32,
+        cancel: *const i32, stats: *mut RtRenderStats, fill_out: *mut i64 /* [2] */,
+    ) -> c_int;
+
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_abi_version() -> c_int;
     pub fn rt_device_count() -> c_int;

@@ -20,6 +20,8 @@
  *                          target with sparse pixel-list passes)
  *   rt_scene_view, rt_accum_reproject: no counterpart either (camera views of one scene, and an accumulator's
  *                          history carried across a camera move)
+ *   rt_accum_holes, rt_accum_fill: no counterpart either (after a reprojection, samples only for the pixels that
+ *                          received no history)
  *
  * Conventions (mirroring the reference's):
  *   - a scene is immutable after creation and may be shared by concurrent rt_render calls
@@ -49,7 +51,8 @@ extern "C" {
                              the version stays 3; likewise progressive accumulation (rt_accum_*, rt_denoise_var*) and
                              the error-target calls (rt_render_pixels*, rt_accum_add_pixels, rt_accum_add_sub_pixels*,
                              rt_accum_counts, rt_accum_select*) and the views and reprojection (rt_scene_view,
-                             rt_scene_get_view, rt_accum_reproject) */
+                             rt_scene_get_view, rt_accum_reproject) and the hole fill (rt_accum_holes*,
+                             rt_accum_fill) */
 
 /* return codes */
 #define RT_OK 0
@@ -390,6 +393,40 @@ int rt_scene_get_view(const rt_scene* scene, double view_out[10]);
  * full-frame passes every K_p >= 2, so rt_accum_select and the sparse merges work unchanged. src is only read. */
 int rt_accum_reproject(void* dst, void* src, const rt_scene* dst_view, const rt_scene* src_view, uint32_t flags,
                        int32_t max_n, int64_t* n_valid);
+
+/* Filling the holes of a reprojection ---------------------------------------------- */
+/* The pixels of a seeded accumulator (one that rt_accum_reproject wrote as dst, until rt_accum_reset or the next
+ * reprojection into it) that need samples. Pixel p = row * width + col is listed iff
+ *   K_p < 2   (a hole: no history, or not yet two passes), or
+ *   period > 0 and (col + 3 * row) mod period == phase   (the refresh pattern: every pixel once in `period` views).
+ * period >= 0, 0 <= phase < max(period, 1), cap >= 0 (pixels_out may be NULL when cap = 0), a non-null accum and n_out,
+ * a seeded accumulator: RT_E_INVAL otherwise, before any device call (the seeded state is asked for last).
+ * pixels_out receives the ids in ascending order, at most cap of them; *n_out is always the full count, *n_holes
+ * (nullable) the count of pixels with K_p < 2. The list is deterministic: a ballot compaction, no atomics on the
+ * order. */
+int rt_accum_holes(void* accum, int32_t period, int32_t phase, uint32_t* pixels_out, int64_t cap, int64_t* n_out,
+                   int64_t* n_holes);
+/* The same into a device buffer of the accumulator's device, enqueued on `stream`; the call waits for the list and
+ * then writes *n_out and *n_holes on the host. */
+int rt_accum_holes_device(void* accum, int32_t period, int32_t phase, void* d_pixels, int64_t cap, int64_t* n_out,
+                          int64_t* n_holes, void* stream);
+/* Two sparse passes that give every hole of a seeded accumulator two passes. params as rt_accum_add_pixels takes them
+ * (the whole frame, the accumulator's device, spp >= 4; RT_FLAG_MIS passes through, RT_FLAG_FP32 and
+ * RT_FLAG_MESH_NEAREST are RT_E_INVAL); period and phase as rt_accum_holes. Every check runs before any device call.
+ *   pass 1 renders the list of rt_accum_holes(period, phase) with params->seed and merges it with n = floor(spp / 4);
+ *   pass 2 renders the pixels that still have K_p < 2 with seed2 and merges them the same way.
+ * The lists stay on the device; an empty list launches nothing. fill_out (nullable) receives the two lists' lengths,
+ * stats (nullable) the two renders' sums (samples = (fill_out[0] + fill_out[1]) * 4 * floor(spp / 4)). A hole's sums
+ * are zeros, so afterwards it holds S = n m1 + n m2 with counts (2, 2 n): bit for bit what two rt_accum_add calls with
+ * the same seeds and spp give that pixel. A refreshed pixel with history gains (1, n).
+ * On RT_OK the accumulator is covered: every K_p >= 2, and it is accepted wherever K >= 1 or K >= 2 is asked for
+ * (rt_accum_resolve* with the variance, rt_accum_select*, rt_accum_add_pixels, rt_accum_add_sub_pixels*, src of
+ * rt_accum_reproject) although rt_accum_info keeps reporting the full-frame passes since the reprojection, possibly 0.
+ * rt_accum_reset and rt_accum_reproject (on dst) clear the state; full-frame merges keep it. A cancelled pass merges
+ * nothing and returns RT_CANCELLED (the passes before it stay merged); the accumulator is then not covered, and a
+ * later rt_accum_fill completes it. */
+int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* params, uint64_t seed2, int32_t period,
+                  int32_t phase, const volatile int32_t* cancel, rt_render_stats* stats, int64_t fill_out[2]);
 
 const char* rt_last_error(void);
 int rt_abi_version(void);

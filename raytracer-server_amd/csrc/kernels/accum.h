@@ -32,5 +32,11 @@ size_t select_scratch_bytes(long npix);
 hipError_t launch_accum_select(const double* S, const float* var, const uint32_t* cnt, int64_t N, int width, int height,
                                float abs_tol, float rel_tol, int32_t max_n, void* scratch, uint32_t* out, long cap,
                                uint32_t* total, hipStream_t st);
+// The hole list of a seeded accumulator (rt_ffi.h rt_accum_holes): the ids of the pixels with
+// K_p < 2, and, with period > 0, of those with (col + 3 row) mod period == phase, ascending, by the selection's
+// compaction. cnt: the per-pixel counts; scratch: select_scratch_bytes(npix) bytes, 8-byte aligned. At most cap ids go
+// to out; *total (device) is the full count, *n_holes (device, 8-byte aligned) the pixels with K_p < 2.
+hipError_t launch_accum_holes(const uint32_t* cnt, int width, int height, int32_t period, int32_t phase, void* scratch,
+                              uint32_t* out, long cap, uint32_t* total, unsigned long long* n_holes, hipStream_t st);
 
 }  // namespace rt

@@ -7,6 +7,8 @@
 // Rendering to an error target (restated by tests/adapt_ref.py):
 //   k_accum_cnt_fill, k_accum_add_list, k_accum_resolve_cnt — per-pixel counts (K_p, N_p) and sparse merges.
 //   k_select_count / k_select_scan / k_select_write — the pixels whose estimated error is above a target, ascending.
+// Filling the holes of a reprojection (restated by tests/fill_ref.py):
+//   k_holes_count — the pixels without two passes, and a refresh pattern; feeds k_select_scan / k_select_write.
 #include <hip/hip_runtime.h>
 
 #include "accum.h"
@@ -195,6 +197,40 @@ __global__ __launch_bounds__(256) void k_select_count(const double2* __restrict_
     if (threadIdx.x == 0) block_count[blockIdx.x] = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
 }
 
+// Pass 1 of the hole list of a seeded accumulator (tests/fill_ref.py restates it): pixel p is listed
+// iff K_p < 2, or period > 0 and (col + 3 row) mod period == phase. Ballots and block counts as k_select_count stores
+// them, for k_select_scan and k_select_write. *n_holes counts the pixels with K_p < 2: one vector atomic per block on
+// an integer (order-free); the list's order never depends on it.
+__global__ __launch_bounds__(256) void k_holes_count(const uint2* __restrict__ cnt, int width, long npix, int32_t period,
+                                                     int32_t phase, unsigned long long* __restrict__ masks,
+                                                     uint32_t* __restrict__ block_count,
+                                                     unsigned long long* __restrict__ n_holes) {
+    __shared__ uint32_t s_n[4], s_h[4];
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    bool hole = false, act = false;
+    if (p < npix) {
+        hole = cnt[p].x < 2u;
+        act = hole;
+        if (period > 0) {  // npix fits an int32 (rt_accum_create), so 32-bit divisions do
+            const uint32_t row = (uint32_t)p / (uint32_t)width, col = (uint32_t)p - row * (uint32_t)width;
+            act = act || (int32_t)(((uint64_t)col + 3ull * (uint64_t)row) % (uint64_t)(uint32_t)period) == phase;
+        }
+    }
+    const unsigned long long mk = __ballot(act), mh = __ballot(hole);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        masks[(size_t)blockIdx.x * 4 + wave] = mk;
+        s_n[wave] = (uint32_t)__popcll(mk);
+        s_h[wave] = (uint32_t)__popcll(mh);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        block_count[blockIdx.x] = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+        const uint32_t h = (s_h[0] + s_h[1]) + (s_h[2] + s_h[3]);
+        if (h != 0u) atomicAdd(n_holes, (unsigned long long)h);
+    }
+}
+
 // Pass 2 (one block of 1024 threads): the exclusive scan of the block counts, in place; *total = their sum. Each thread
 // sums a contiguous segment, the 1024 segment sums are scanned in LDS, then each thread writes its segment's offsets.
 __global__ __launch_bounds__(1024) void k_select_scan(uint32_t* __restrict__ block_count, long nblocks,
@@ -254,6 +290,24 @@ hipError_t launch_accum_select(const double* S, const float* var, const uint32_t
     hipLaunchKernelGGL(k_select_count, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<const double2*>(S),
                        reinterpret_cast<const float4*>(var), reinterpret_cast<const uint2*>(cnt), (double)N, width,
                        height, (double)abs_tol, (double)rel_tol, max_n, masks, counts);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, st, counts, nb, total);
+    if (cap > 0 && out)
+        hipLaunchKernelGGL(k_select_write, dim3((unsigned)nb), dim3(256), 0, st, masks, counts, npix, out, cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_accum_holes(const uint32_t* cnt, int width, int height, int32_t period, int32_t phase, void* scratch,
+                              uint32_t* out, long cap, uint32_t* total, unsigned long long* n_holes, hipStream_t st) {
+    const long npix = (long)width * height;
+    if (npix <= 0 || !cnt || !scratch || !total || !n_holes || period < 0 || phase < 0 || phase >= (period > 1 ? period : 1))
+        return hipErrorInvalidValue;
+    const long nb = select_blocks(npix);
+    unsigned long long* masks = (unsigned long long*)scratch;
+    uint32_t* counts = (uint32_t*)(masks + (size_t)nb * 4);
+    hipError_t e = hipMemsetAsync(n_holes, 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_holes_count, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<const uint2*>(cnt), width,
+                       npix, period, phase, masks, counts, n_holes);
     hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(1024), 0, st, counts, nb, total);
     if (cap > 0 && out)
         hipLaunchKernelGGL(k_select_write, dim3((unsigned)nb), dim3(256), 0, st, masks, counts, npix, out, cap);

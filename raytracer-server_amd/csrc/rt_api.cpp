@@ -1743,6 +1743,9 @@ struct rt_accum {
     // seeded by rt_accum_reproject: S, Q and the per-pixel counts hold reprojected history although
     // no full-frame pass has been merged since (K = N = 0), so the next merge adds instead of storing
     bool seeded = false;
+    // covered by rt_accum_fill: a seeded accumulator whose every K_p >= 2 without two full-frame
+    // passes; it passes wherever K >= 1 or K >= 2 is asked for
+    bool covered = false;
     uint32_t* cnt() const { return (uint32_t*)adapt; }
     size_t npix() const { return (size_t)width * height; }
     size_t sub_bytes() const { return npix() * 12 * sizeof(double); }
@@ -1819,6 +1822,7 @@ int check_accum_sub(const char* who, const rt_accum* a, const void* sub, int32_t
 
 int check_accum_resolve(const char* who, const rt_accum* a, const void* var) {
     if (!a) return fail(RT_E_INVAL, std::string(who) + ": null argument");
+    if (a->covered) return RT_OK;  // every K_p >= 2 (rt_accum_fill)
     if (a->K < 1) return fail(RT_E_INVAL, std::string(who) + ": no pass accumulated");
     if (var && a->K < 2) return fail(RT_E_INVAL, std::string(who) + ": the variance needs at least two passes");
     return RT_OK;
@@ -1902,6 +1906,7 @@ int rt_accum_reset(void* accum) {
     a->N = 0;
     a->sparse = false;  // the per-pixel counts are forgotten with the passes
     a->seeded = false;  // and so is reprojected history
+    a->covered = false;
     return RT_OK;
 }
 
@@ -2180,7 +2185,7 @@ int check_sparse(const char* who, const rt_accum* a, const void* pixels, int64_t
         const int rc = check_pixel_list(who, (const uint32_t*)pixels, n_pixels, (int64_t)a->npix());
         if (rc != RT_OK) return rc;
     }
-    if (a->K < 2) return fail(RT_E_INVAL, w + ": a sparse pass needs two full-frame passes first");
+    if (a->K < 2 && !a->covered) return fail(RT_E_INVAL, w + ": a sparse pass needs two full-frame passes first");
     return RT_OK;
 }
 
@@ -2204,7 +2209,7 @@ int check_select(const char* who, const rt_accum* a, float abs_tol, float rel_to
     if (!a || !n_out) return fail(RT_E_INVAL, w + ": null argument");
     if (!(abs_tol >= 0.f) || !(rel_tol >= 0.f)) return fail(RT_E_INVAL, w + ": tolerances must be >= 0 and not NaN");
     if (cap < 0 || (cap > 0 && !out)) return fail(RT_E_INVAL, w + ": bad output buffer");
-    if (a->K < 2) return fail(RT_E_INVAL, w + ": the selection needs at least two passes");
+    if (a->K < 2 && !a->covered) return fail(RT_E_INVAL, w + ": the selection needs at least two passes");
     return RT_OK;
 }
 
@@ -2450,7 +2455,8 @@ int rt_accum_reproject(void* dst, void* src, const rt_scene* dst_view, const rt_
     if (dst_view->root != src_view->root) return fail(RT_E_INVAL, "rt_accum_reproject: the two views do not share a base");
     if (max_n < 1) return fail(RT_E_INVAL, "rt_accum_reproject: max_n must be >= 1");
     if (flags & ~RT_FLAG_MESH_NEAREST) return fail(RT_E_INVAL, "rt_accum_reproject: unknown flag");
-    if (s->K < 2) return fail(RT_E_INVAL, "rt_accum_reproject: src needs at least two full-frame passes");
+    if (s->K < 2 && !s->covered)
+        return fail(RT_E_INVAL, "rt_accum_reproject: src needs at least two full-frame passes");
     int rc = need_device("rt_accum_reproject", d->device);
     if (rc == RT_OK) rc = accum_ready(d, true, false);
     if (rc == RT_OK) rc = adapt_ready(d);
@@ -2501,6 +2507,7 @@ int rt_accum_reproject(void* dst, void* src, const rt_scene* dst_view, const rt_
     d->N = 0;
     d->sparse = false;
     d->seeded = false;
+    d->covered = false;
     CallStream cs;
     HIP_TRY(cs.init());
     unsigned long long count = 0;
@@ -2514,6 +2521,146 @@ int rt_accum_reproject(void* dst, void* src, const rt_scene* dst_view, const rt_
     d->seeded = true;  // the next merge adds
     if (n_valid) *n_valid = (int64_t)count;
     return RT_OK;
+}
+
+// Filling the holes of a reprojection -------------------------------------------------------
+
+namespace {
+
+// The arguments of a hole list that need no device; the seeded state is asked for last, so that every other check
+// can be reached without a GPU.
+int check_holes(const char* who, const rt_accum* a, int32_t period, int32_t phase) {
+    const std::string w(who);
+    if (period < 0) return fail(RT_E_INVAL, w + ": period must be >= 0");
+    if (phase < 0 || phase >= std::max(period, 1)) return fail(RT_E_INVAL, w + ": phase must be in 0 .. max(period, 1) - 1");
+    if (!a->seeded) return fail(RT_E_INVAL, w + ": the accumulator is not seeded by rt_accum_reproject");
+    return RT_OK;
+}
+
+// Lists the holes into d_out (device, cap ids) on `st`, waits, and reads the two counts.
+int holes_run(rt_accum* a, int32_t period, int32_t phase, uint32_t* d_out, int64_t cap, int64_t* n_out, int64_t* n_holes,
+              hipStream_t st) {
+    unsigned long long* d_holes = (unsigned long long*)(adapt_total(a) + 2);
+    hipError_t e = rt::launch_accum_holes(a->cnt(), a->width, a->height, period, phase, adapt_scratch(a), d_out, (long)cap,
+                                          adapt_total(a), d_holes, st);
+    uint32_t total = 0;
+    unsigned long long holes = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, adapt_total(a), sizeof total, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&holes, d_holes, sizeof holes, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_holes: ") + hipGetErrorString(e));
+    *n_out = (int64_t)total;
+    if (n_holes) *n_holes = (int64_t)holes;
+    return RT_OK;
+}
+
+int check_holes_call(const char* who, const rt_accum* a, int32_t period, int32_t phase, int64_t cap, const void* out,
+                     const int64_t* n_out) {
+    const std::string w(who);
+    if (!a || !n_out) return fail(RT_E_INVAL, w + ": null argument");
+    if (cap < 0 || (cap > 0 && !out)) return fail(RT_E_INVAL, w + ": bad output buffer");
+    return check_holes(who, a, period, phase);
+}
+
+}  // namespace
+
+int rt_accum_holes_device(void* accum, int32_t period, int32_t phase, void* d_pixels, int64_t cap, int64_t* n_out,
+                          int64_t* n_holes, void* stream) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_holes_call("rt_accum_holes_device", a, period, phase, cap, d_pixels, n_out);
+    if (rc == RT_OK) rc = need_device("rt_accum_holes_device", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, false);
+    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc != RT_OK) return rc;
+    return holes_run(a, period, phase, (uint32_t*)d_pixels, cap, n_out, n_holes, (hipStream_t)stream);
+}
+
+int rt_accum_holes(void* accum, int32_t period, int32_t phase, uint32_t* pixels_out, int64_t cap, int64_t* n_out,
+                   int64_t* n_holes) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_holes_call("rt_accum_holes", a, period, phase, cap, pixels_out, n_out);
+    if (rc == RT_OK) rc = need_device("rt_accum_holes", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, false);
+    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc != RT_OK) return rc;
+    CallStream cs;
+    HIP_TRY(cs.init());
+    const int64_t dcap = std::min<int64_t>(cap, (int64_t)a->npix());  // the list buffer holds every pixel
+    rc = holes_run(a, period, phase, adapt_list(a), dcap, n_out, n_holes, cs.st);
+    if (rc != RT_OK) return rc;
+    const int64_t n = std::min(*n_out, dcap);
+    if (n > 0) HIP_TRY(hipMemcpy(pixels_out, adapt_list(a), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* p, uint64_t seed2, int32_t period,
+                  int32_t phase, const volatile int32_t* cancel, rt_render_stats* stats, int64_t fill_out[2]) {
+    rt_accum* a = (rt_accum*)accum;
+    int rc = check_accum_add(a, scene, p);
+    if (rc == RT_OK) rc = check_render_pixels("rt_accum_fill", scene, p, nullptr, 0);
+    if (rc == RT_OK) rc = check_holes("rt_accum_fill", a, period, phase);
+    if (rc == RT_OK) rc = need_device("rt_accum_fill", a->device);
+    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc != RT_OK) return rc;
+    CallStream cs;  // destroyed last: after the stats' events and the cancel word have gone back
+    hipError_t ce = cs.init();
+    CancelMirror mirror;
+    if (ce == hipSuccess && cancel) ce = mirror.init();
+    if (ce != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_fill: ") + hipGetErrorString(ce));
+    hipStream_t st = cs.st;
+    rt_render_stats sum, one;
+    std::memset(&sum, 0, sizeof sum);
+    PendingStats ps;
+    int64_t lens[2] = {0, 0};
+    for (int pass = 0; pass < 2; ++pass) {
+        // pass 1: the holes and the refresh pattern; pass 2: what still lacks a second pass. The list stays on the
+        // device; only its length comes back.
+        int64_t n_list = 0;
+        rc = holes_run(a, pass == 0 ? period : 0, pass == 0 ? phase : 0, adapt_list(a), (int64_t)a->npix(), &n_list,
+                       nullptr, st);
+        if (rc != RT_OK) return rc;
+        lens[pass] = n_list;
+        if (n_list == 0) continue;  // an empty list launches nothing
+        if (n_list > (int64_t)INT32_MAX / 4) return fail(RT_E_INVAL, "rt_accum_fill: the list's length * 4 must fit an int32");
+        rt_render_params pp = *p;
+        if (pass == 1) pp.seed = seed2;
+        ps.out = &one;
+        rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), &pp, adapt_list(a), n_list, nullptr, a->stage_sub(), st,
+                                   mirror.dev, &ps);
+        std::string err = g_err;
+        if (rc == RT_OK) {
+            const hipError_t e = wait_stream(st, cancel, &mirror);
+            if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_accum_fill: ") + hipGetErrorString(e); }
+            if (rc == RT_OK) {
+                const int f = ps.finish(&err);
+                if (f < 0) rc = f;
+            }
+            if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
+        } else {
+            (void)hipStreamSynchronize(st);
+        }
+        if (rc < 0) return fail(rc, err);
+        if (rc != RT_OK) break;  // cancelled: this pass merges nothing and the accumulator stays uncovered
+        rc = accum_merge_list(a, adapt_list(a), n_list, a->stage_sub(), p->spp / 4, st);
+        if (rc != RT_OK) return rc;
+        sum.samples += one.samples;
+        sum.vertices += one.vertices;
+        sum.iterations += one.iterations;
+        sum.device_ms += one.device_ms;
+        for (int k = 0; k < 8; ++k) {
+            sum.kernel_ms[k] += one.kernel_ms[k];
+            sum.kernel_launches[k] += one.kernel_launches[k];
+        }
+    }
+    if (stats) *stats = sum;
+    if (fill_out) {
+        fill_out[0] = lens[0];
+        fill_out[1] = lens[1];
+    }
+    if (rc == RT_OK) a->covered = true;  // every K_p >= 2
+    return rc;
 }
 
 // Batch query diagnostics (include/rt_diag.h, kernels/diag_queries.h) -------------------------------------

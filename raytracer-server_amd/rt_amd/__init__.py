@@ -12,6 +12,8 @@ Beyond the reference: render_features / denoise / render_denoised, denoised prev
 to a per-pixel error target with sparse pixel-list passes (rt_render_pixels, rt_accum_select).
 Scene.view / Scene.camera / look_at / Accumulator.reproject_from / render_interactive: camera views of one scene and
 an accumulator's history carried across a camera move (rt_scene_view, rt_accum_reproject).
+Accumulator.holes / Accumulator.fill / render_interactive(fill_spp, refresh) / FILL_DEFAULTS: after a reprojection,
+samples only for the pixels without history (rt_accum_holes, rt_accum_fill).
 
 Everything computes on the GPU through lib/librtamd.so; there is no CPU fallback. Importing this
 module without the built library raises ImportError.
@@ -89,7 +91,8 @@ _EXPORTS = ["rt_scene_load_toml", "rt_scene_create", "rt_scene_destroy", "rt_sce
             "rt_accum_add_sub_device", "rt_accum_resolve", "rt_accum_resolve_device", "rt_denoise_var",
             "rt_denoise_var_device", "rt_render_pixels", "rt_render_pixels_device", "rt_accum_add_pixels",
             "rt_accum_add_sub_pixels", "rt_accum_add_sub_pixels_device", "rt_accum_counts", "rt_accum_select",
-            "rt_accum_select_device", "rt_scene_view", "rt_scene_get_view", "rt_accum_reproject"]
+            "rt_accum_select_device", "rt_scene_view", "rt_scene_get_view", "rt_accum_reproject", "rt_accum_holes",
+            "rt_accum_holes_device", "rt_accum_fill"]
 
 
 def _load():
@@ -148,6 +151,9 @@ def _load():
     L.rt_scene_view.argtypes = [vp, P(View), P(vp)]
     L.rt_scene_get_view.argtypes = [vp, P(View)]
     L.rt_accum_reproject.argtypes = [vp, vp, vp, vp, U32, I, P(I64)]
+    L.rt_accum_holes.argtypes = [vp, I, I, P(U32), I64, P(I64), P(I64)]
+    L.rt_accum_holes_device.argtypes = [vp, I, I, vp, I64, P(I64), P(I64), vp]
+    L.rt_accum_fill.argtypes = [vp, vp, P(RenderParams), ctypes.c_uint64, I, I, P(I), P(RenderStats), P(I64)]
     L.rt_last_error.restype = ctypes.c_char_p
     L.rt_last_error.argtypes = []
     L.rt_abi_version.argtypes = []
@@ -587,6 +593,36 @@ class Accumulator:
                                       FLAG_MESH_NEAREST if mesh_nearest else 0, max_n, ctypes.byref(n)))
         return n.value
 
+    def holes(self, period=0, phase=0, cap=None):
+        """The pixels of a seeded accumulator (after reproject_from) that need samples: those with fewer than two
+        passes and, with period > 0, those with (col + 3 * row) % period == phase, ascending ids row * width + col
+        (rt_accum_holes). Returns (ids uint32[min(count, cap)], n_holes): n_holes counts the pixels with
+        fewer than two passes; cap=None: every listed pixel."""
+        cap = self.width * self.height if cap is None else cap
+        ids = np.zeros(max(1, cap), dtype=np.uint32)
+        n, nh = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(lib.rt_accum_holes(self._h, period, phase, _ptr(ids, ctypes.c_uint32), cap, ctypes.byref(n),
+                                  ctypes.byref(nh)))
+        return ids[:min(n.value, cap)], nh.value
+
+    def fill(self, scene, spp, seed, seed2, period=0, phase=0, mis=False, cancel=None):
+        """Gives every hole of a seeded accumulator two passes of `spp` (seeds `seed` and `seed2`) without a full-frame
+        pass, and the pixels of the refresh pattern (period, phase: see holes) one (rt_accum_fill).
+        Afterwards the accumulator is covered: resolve with the variance, select, add_pixels and reproject_from (as
+        src) work although info() reports no full-frame pass. Returns the two renders' summed stats with
+        stats["fill"] = (pass-1 list length, pass-2 list length); stats["cancelled"] is True when the cancel word
+        stopped a pass (that pass merged nothing, the accumulator is not covered, a later fill completes it)."""
+        p = make_params(self.width, self.height, spp, seed, None, FLAG_MEGAKERNEL | (FLAG_MIS if mis else 0),
+                        self.device, 1)
+        st = RenderStats()
+        lens = (ctypes.c_int64 * 2)()
+        rc = _check(lib.rt_accum_fill(self._h, scene.handle, ctypes.byref(p), seed2, period, phase,
+                                      ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st), lens))
+        out = st.as_dict()
+        out["fill"] = (int(lens[0]), int(lens[1]))
+        out["cancelled"] = rc == RT_CANCELLED
+        return out
+
 
 def look_at(pos, target, up=(0.0, 1.0, 0.0), fov=0.5135):
     """The arguments of Scene.view for a camera at pos looking at target: dict(pos, dir, right, fov) with
@@ -734,8 +770,21 @@ def render_to_error(scene, width, height, abs_tol=None, max_spp=512, first=None,
 
 # Orbiting a scene ---------------------------------------------------------------------------
 
+# The measured choice of render_interactive's fill_spp and refresh (the function's own defaults stay
+# 0, 0: the flow of §14). Pass them as render_interactive(..., **FILL_DEFAULTS), or **fill_defaults_for(scene).
+FILL_DEFAULTS = dict(fill_spp=16, refresh=4)
+
+
+def fill_defaults_for(scene):
+    """render_interactive's fill_spp and refresh for `scene`: FILL_DEFAULTS for a scene of spheres and planes, off
+    (0, 0) for a scene with meshes. On the MI355X the fill won on cornell_box (0.70 of the per-view time at a lower
+    RMSE) and lost on the mesh scenes, whose list renders run the fused per-vertex walk: cubes no faster at the same
+    RMSE, flying_unicorn 3.3 times slower."""
+    return dict(FILL_DEFAULTS) if scene.info()["meshes"] == 0 else dict(fill_spp=0, refresh=0)
+
+
 def render_interactive(scene, views, width, height, first=8, max_n=64, abs_tol=None, rel_tol=0.0, view_spp=0,
-                       pass_spp=16, seed=0x5EED, device=0, cancel=None, **denoise_params):
+                       pass_spp=16, seed=0x5EED, device=0, cancel=None, fill_spp=0, refresh=0, **denoise_params):
     """A generator over camera views of one scene that carries the accumulated samples across the camera moves. views:
     an iterable (read lazily, one view per frame) of Scene.view keyword dicts (look_at makes them; a "view_spp" key
     overrides the budget for that view) or Scene objects that are views of `scene`. For each view it
@@ -748,8 +797,15 @@ def render_interactive(scene, views, width, height, first=8, max_n=64, abs_tol=N
       4. resolves, computes the view's features and filters with denoise_var (denoise_params: levels / sigma_*),
     and yields (rgb[h, w, 3] u8, fraction of pixels that received history, camera samples traced for this view). Pass k
     of the whole sequence renders with pass_seed(seed, k): one counter over all views, so no pass repeats a seed the
-    history already holds. A raised cancel word ends the generator."""
+    history already holds. A raised cancel word ends the generator.
+    fill_spp > 0 replaces step 2, for every view after the first, by Accumulator.fill: two sparse
+    passes of fill_spp over the pixels without history only, plus, with refresh = R > 0, one pass over the pixels
+    with (col + 3 * row) % R == view index % R, so that every pixel receives a fresh pass once in R views (refresh = 0:
+    a pixel with history is never sampled again by step 2, and the nearest-subpixel fetch's resampling error compounds
+    from view to view). The first view still gets its two full passes; fill_spp = 0 is the flow above, bit for bit.
+    FILL_DEFAULTS holds the measured choice of (fill_spp, refresh)."""
     half = max(4, first // 4 * 4)
+    fill_spp = max(4, fill_spp // 4 * 4) if fill_spp > 0 else 0
     pass_spp = max(4, pass_spp // 4 * 4)
     npix = width * height
     default_spp = view_spp
@@ -769,11 +825,19 @@ def render_interactive(scene, views, width, height, first=8, max_n=64, abs_tol=N
             else:
                 acc.reset()
             samples = 0
-            for _ in range(2):
-                if acc.add(v, half, pass_seed(seed, k), cancel=cancel)["cancelled"]:
+            if fill_spp > 0 and prev_view is not None:
+                st = acc.fill(v, fill_spp, pass_seed(seed, k), pass_seed(seed, k + 1), period=refresh,
+                              phase=i % refresh if refresh > 0 else 0, cancel=cancel)
+                if st["cancelled"]:
                     return
-                k += 1
-                samples += npix * half
+                k += 2
+                samples += sum(st["fill"]) * fill_spp
+            else:
+                for _ in range(2):
+                    if acc.add(v, half, pass_seed(seed, k), cancel=cancel)["cancelled"]:
+                        return
+                    k += 1
+                    samples += npix * half
             while abs_tol is not None and samples + pass_spp <= view_spp * npix:
                 ids, _ = acc.select(abs_tol, rel_tol, max_n)
                 ids = ids[:(view_spp * npix - samples) // pass_spp]

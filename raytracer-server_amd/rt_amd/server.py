@@ -20,6 +20,9 @@ Run:  PORT=8080 python -m rt_amd.server <scenes dir>
       RT_REPROJECT=<max_n> together with RT_PROGRESSIVE or RT_TARGET_ERROR: a connection keeps its last accumulator
       and view, and a request for the same scene starts from the reprojected history (rt_amd.render_interactive,
       DESIGN.md §14; at most max_n samples per subpixel are inherited).
+      RT_REPROJECT_FILL=<spp>[,<refresh>] together with RT_REPROJECT: from a connection's second request on, the two
+      full-frame passes are replaced by two sparse passes of <spp> over the pixels that received no history, and every
+      pixel gets one fresh pass once in <refresh> requests (0, the default: never). Unset: unchanged.
 Beyond the reference's protocol the render message takes an optional camera, {"type": "render", ..., "camera":
 {"pos": [x, y, z], "dir": [x, y, z], "right": [x, y, z] (optional), "fov": f (optional)}}: the scene is rendered
 through Scene.view of it. Without it nothing changes; a bad camera is a logged error, like a bad scene name.
@@ -74,6 +77,20 @@ def parse_camera(m):
             raise ValueError(f"bad camera fov {cam['fov']!r}")
         out["fov"] = float(cam["fov"])
     return out
+
+
+def parse_fill(text):
+    """RT_REPROJECT_FILL's value "<spp>[,<refresh>]" as (fill_spp, refresh); (0, 0) for None (unset: no fill).
+    ValueError for anything but one or two integers with spp >= 4 and refresh >= 0."""
+    if text is None:
+        return 0, 0
+    parts = text.split(",")
+    if len(parts) not in (1, 2):
+        raise ValueError(f"bad RT_REPROJECT_FILL {text!r}")
+    spp, refresh = int(parts[0]), int(parts[1]) if len(parts) == 2 else 0
+    if spp < 4 or refresh < 0:
+        raise ValueError(f"bad RT_REPROJECT_FILL {text!r}: spp must be >= 4 and refresh >= 0")
+    return spp, refresh
 
 
 def gpu_band_renderer(device=0, fp32=False):
@@ -251,6 +268,9 @@ class InteractiveJob:
         self.max_n = max_n
         self.first = first
         self.abs_tol = abs_tol
+        # RT_REPROJECT_FILL=<spp>[,<refresh>]: after the first request, two sparse passes of <spp> over the pixels
+        # without history (and one over a refresh pattern) instead of the two full-frame passes
+        self.fill_spp, self.refresh = parse_fill(os.environ.get("RT_REPROJECT_FILL"))
         self.device = device
         self.denoise_params = denoise_params
         self.cancel = ctypes.c_int32(1)  # starts cancelled == not running
@@ -286,7 +306,8 @@ class InteractiveJob:
             self._drop()
             self._frames = rt_amd.render_interactive(base, self._views(), width, height, first=self.first,
                                                      max_n=self.max_n, abs_tol=self.abs_tol, seed=seed,
-                                                     device=self.device, cancel=self.cancel, **self.denoise_params)
+                                                     device=self.device, cancel=self.cancel, fill_spp=self.fill_spp,
+                                                     refresh=self.refresh, **self.denoise_params)
             self._key = key
             self._base = base  # keeps id(base) unique while the generator lives
         self._next_view = dict(scene.camera(), view_spp=spp)
@@ -413,7 +434,10 @@ def main(argv=None):
         print(f"RT_REPROJECT={max_n}: whole-frame jobs that inherit up to {max_n} samples per subpixel from the "
               f"connection's last view; two passes of {first} spp per request"
               + (f", then sparse passes to the error target {abs_tol} within the request's spp" if abs_tol is not None
-                 else ""), file=sys.stderr)
+                 else "")
+              + (f"; RT_REPROJECT_FILL={os.environ['RT_REPROJECT_FILL']}: after a connection's first request the "
+                 "two passes cover only the pixels without history" if "RT_REPROJECT_FILL" in os.environ else ""),
+              file=sys.stderr)
         server = Server(scenes, job_factory=lambda send: InteractiveJob(send, max_n, first=first, abs_tol=abs_tol))
     elif "RT_TARGET_ERROR" in os.environ:
         # rendering to an error target: whole frames, sparse passes over the pixels still above it
