@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -37,12 +39,15 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP,                        \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                    \
+// A failed HIP call as a return code: RT_E_OOM when the device is out of memory, RT_E_HIP otherwise.
+int oom_or_hip(hipError_t e, const std::string& what) {
+    return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, what + ": " + hipGetErrorString(e));
+}
+
+#define HIP_TRY(expr)                                       \
+    do {                                                    \
+        hipError_t e_ = (expr);                             \
+        if (e_ != hipSuccess) return oom_or_hip(e_, #expr); \
     } while (0)
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -1010,6 +1015,119 @@ struct PendingStats {
     }
 };
 
+// The tail of the _device render forms: with stats, the call is synchronous with respect to the stream (rt_ffi.h).
+// rc: what the enqueue returned; ps: null without stats.
+int stats_sync(int rc, hipStream_t st, PendingStats* ps) {
+    if (rc < 0 || !ps) return rc;
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("stats sync: ") + hipGetErrorString(e));
+    std::string err;
+    const int f = ps->finish(&err);
+    return f < 0 ? fail(f, err) : rc;
+}
+
+// Device memory that lives for one call, carved into 16-byte aligned parts: part() every part (its offset comes
+// back), alloc() once, at<T>() the parts. The destructor frees it, so no path out of the call has a free of its own;
+// declare it before the call's stream (CallStream, whose destructor waits), so the memory outlives the work on it.
+struct DeviceBlock {
+    char* base = nullptr;
+    size_t bytes = 0;
+    DeviceBlock() = default;
+    DeviceBlock(const DeviceBlock&) = delete;
+    DeviceBlock& operator=(const DeviceBlock&) = delete;
+    ~DeviceBlock() {
+        if (base) (void)hipFree(base);
+    }
+    size_t part(size_t n) {
+        const size_t at = bytes;
+        bytes += align_up(n, 16);
+        return at;
+    }
+    hipError_t alloc() {
+        const hipError_t e = hipMalloc((void**)&base, bytes);
+        if (e != hipSuccess) base = nullptr;
+        return e;
+    }
+    template <class T>
+    T* at(size_t off) const { return (T*)(base + off); }
+};
+
+// A stream for one call: waited for and destroyed when the call returns.
+struct CallStream {
+    hipStream_t st = nullptr;
+    CallStream() = default;
+    CallStream(const CallStream&) = delete;
+    CallStream& operator=(const CallStream&) = delete;
+    hipError_t init() { return hipStreamCreateWithFlags(&st, hipStreamNonBlocking); }
+    // the destructor's work, for a call that ends with copies whose outcome it reports: the one wait of that path
+    hipError_t close() {
+        if (!st) return hipSuccess;
+        const hipError_t e = hipStreamSynchronize(st);
+        (void)hipStreamDestroy(st);
+        st = nullptr;
+        return e;
+    }
+    ~CallStream() { (void)close(); }
+};
+
+// What a host render call that waits for its render owns (rt_render, rt_render_pixels, rt_accum_add,
+// rt_accum_add_pixels, rt_accum_fill). Members go in reverse order, and the order is the rule: the stream goes first,
+// and its destructor waits for it, so on every path out of the call nothing enqueued can still write the stats'
+// pinned word, poll the cancel word or touch the call's memory when the stats' events are destroyed, the word goes
+// back to the pool (where the next render may take it) and the memory is freed.
+struct RenderCall {
+    DeviceBlock mem;  // the call's device buffers, for a call that has any: part() them before init()
+    CancelMirror mirror;
+    rt_render_stats local;  // where the stats go when the caller wants none
+    PendingStats ps;
+    CallStream cs;
+    const volatile int32_t* cancel = nullptr;
+
+    // One device-to-host copy of the readback; a null dst is skipped.
+    struct Copy {
+        void* dst;
+        const void* src;
+        size_t bytes;
+    };
+
+    // The stream, the memory parted so far and, for a cancellable call, the mirror of the caller's flag.
+    int init(const char* who, const volatile int32_t* cancel_flag, rt_render_stats* stats) {
+        cancel = cancel_flag;
+        ps.out = stats ? stats : &local;
+        hipError_t e = cs.init();
+        if (e == hipSuccess && mem.bytes) e = mem.alloc();
+        if (e == hipSuccess && cancel) e = mirror.init();
+        return e == hipSuccess ? RT_OK : oom_or_hip(e, who);
+    }
+
+    // After render_enqueue / render_pixels_enqueue on cs.st returned rc: waits for the render while relaying the
+    // cancel flag, copies back, completes the stats; RT_CANCELLED when the flag is up by then (the caller merges
+    // nothing). An enqueue that failed left its message in g_err, and the stream is drained of whatever it did
+    // enqueue before anything it used is released.
+    int finish(const char* who, int rc, std::initializer_list<Copy> readback = {}) {
+        if (rc != RT_OK) {
+            (void)hipStreamSynchronize(cs.st);
+            return rc;
+        }
+        // wait for the render first (relaying the cancel flag), then copy back: a copy into the
+        // caller's pageable buffers would block inside hipMemcpyAsync until the kernel ends, with
+        // nobody relaying the flag
+        hipError_t e = wait_stream(cs.st, cancel, &mirror);
+        bool copied = false;
+        for (const Copy& c : readback)
+            if (e == hipSuccess && c.dst) {
+                e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, cs.st);
+                copied = true;
+            }
+        if (e == hipSuccess && copied) e = cs.close();
+        if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        std::string err;
+        const int f = ps.finish(&err);
+        if (f < 0) return fail(f, err);
+        return cancel && *cancel ? RT_CANCELLED : RT_OK;
+    }
+};
+
 // The kernels' view of `p` on the uploaded scene `ds`: frame, tile, samples, seed, camera frame and the Cfg<F>
 // feature bits (no output pointers, no scheduling).
 rt::RenderArgs make_render_args(const rt_scene* s, const rt_render_params* p, const rt::DevScene& ds) {
@@ -1040,6 +1158,15 @@ rt::RenderArgs make_render_args(const rt_scene* s, const rt_render_params* p, co
     rt::host::camera_frame(s->cam_dir, s->cam_right, s->cam_fov, p->width, p->height, a.cx, a.cy);
     a.inv_n = a.n_samples > 0 ? 1. / (double)a.n_samples : 0.0;
     return a;
+}
+
+// The RGB8 of a width x height buffer of subpixel means: rt_render's own (k_finalize_f64), byte for byte.
+hipError_t finalize_rgb(int32_t width, int32_t height, const double* d_sub, uint8_t* d_rgb, hipStream_t st) {
+    rt::RenderArgs a{};
+    a.tw = width;
+    a.th = height;
+    a.rgb_out = d_rgb;
+    return rt::launch_finalize_f64(a, d_sub, st);
 }
 
 // Enqueue one render on `st` (device buffers); returns without waiting for the device (except in
@@ -1285,14 +1412,9 @@ int rt_render_device(const rt_scene* scene, const rt_render_params* params, void
     hipStream_t st = (hipStream_t)stream;
     PendingStats ps;
     ps.out = stats;
-    int rc = render_enqueue(const_cast<rt_scene*>(scene), params, (uint8_t*)d_rgb, (double*)d_sub, st, nullptr, nullptr,
-                            stats ? &ps : nullptr);
-    if (rc < 0 || !stats) return rc;
-    const hipError_t e = hipStreamSynchronize(st);  // stats: synchronous with respect to the stream (rt_ffi.h)
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("stats sync: ") + hipGetErrorString(e));
-    std::string err;
-    const int f = ps.finish(&err);
-    return f < 0 ? fail(f, err) : rc;
+    const int rc = render_enqueue(const_cast<rt_scene*>(scene), params, (uint8_t*)d_rgb, (double*)d_sub, st, nullptr,
+                                  nullptr, stats ? &ps : nullptr);
+    return stats_sync(rc, st, stats ? &ps : nullptr);
 }
 
 int rt_render(const rt_scene* scene, const rt_render_params* p, uint8_t* rgb_out, double* sub_out,
@@ -1301,49 +1423,17 @@ int rt_render(const rt_scene* scene, const rt_render_params* p, uint8_t* rgb_out
     int rc = check_params(p);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
-    size_t npix = (size_t)p->tile_w * p->tile_h;
+    const size_t npix = (size_t)p->tile_w * p->tile_h;
     if (npix == 0) return RT_OK;
-    uint8_t* d_rgb = nullptr;
-    double* d_sub = nullptr;
-    hipStream_t st = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    hipError_t e = hipMalloc(&d_rgb, npix * 3);
-    if (e == hipSuccess && sub_out) e = hipMalloc(&d_sub, npix * 12 * sizeof(double));
-    CancelMirror mirror;
-    if (e == hipSuccess && cancel) e = mirror.init();
-    if (e != hipSuccess) {
-        if (d_rgb) (void)hipFree(d_rgb);
-        if (d_sub) (void)hipFree(d_sub);
-        (void)hipStreamDestroy(st);
-        return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, std::string("output buffers: ") + hipGetErrorString(e));
-    }
-    rt_render_stats local;
-    PendingStats ps;
-    ps.out = stats ? stats : &local;
-    rc = render_enqueue(const_cast<rt_scene*>(scene), p, d_rgb, d_sub, st, mirror.dev, cancel, &ps);
-    std::string err = g_err;
-    if (rc == RT_OK) {
-        // wait for the render first (relaying the cancel flag), then copy back: a copy into the
-        // caller's pageable buffers would block inside hipMemcpyAsync until the kernel ends, with
-        // nobody relaying the flag
-        e = wait_stream(st, cancel, &mirror);
-        if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, d_rgb, npix * 3, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && sub_out) e = hipMemcpyAsync(sub_out, d_sub, npix * 12 * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("readback: ") + hipGetErrorString(e); }
-        if (rc == RT_OK) {
-            const int f = ps.finish(&err);
-            if (f < 0) rc = f;
-        }
-        if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
-    } else {
-        (void)hipStreamSynchronize(st);
-    }
-    (void)hipFree(d_rgb);
-    if (d_sub) (void)hipFree(d_sub);
-    (void)hipStreamDestroy(st);
-    if (rc < 0) return fail(rc, err);
-    return rc;
+    RenderCall call;
+    const size_t b_sub = npix * 12 * sizeof(double);
+    const size_t at_sub = call.mem.part(sub_out ? b_sub : 0), at_rgb = call.mem.part(npix * 3);
+    rc = call.init("rt_render", cancel, stats);
+    if (rc != RT_OK) return rc;
+    uint8_t* d_rgb = call.mem.at<uint8_t>(at_rgb);
+    double* d_sub = sub_out ? call.mem.at<double>(at_sub) : nullptr;
+    rc = render_enqueue(const_cast<rt_scene*>(scene), p, d_rgb, d_sub, call.cs.st, call.mirror.dev, cancel, &call.ps);
+    return call.finish("rt_render", rc, {{rgb_out, d_rgb, npix * 3}, {sub_out, d_sub, b_sub}});
 }
 
 int32_t rt_band_plan(int32_t tile_h, int32_t n_workers, int32_t band_rows, int32_t cap, int32_t* first_row,
@@ -1493,17 +1583,16 @@ int rt_trace_rays_flags(const rt_scene* scene, int32_t device, uint32_t flags, i
     rt::DevScene ds;
     int rc = upload(const_cast<rt_scene*>(scene), device, &ds);
     if (rc != RT_OK) return rc;
-    size_t v3 = (size_t)n * 3 * sizeof(double);
-    char* buf = nullptr;
-    size_t total = 4 * v3 + (size_t)n * sizeof(double) + (size_t)n * sizeof(int32_t);
-    HIP_TRY(hipMalloc((void**)&buf, total));
-    double* d_o = (double*)buf;
-    double* d_d = (double*)(buf + v3);
-    double* d_pos = (double*)(buf + 2 * v3);
-    double* d_n = (double*)(buf + 3 * v3);
-    double* d_t = (double*)(buf + 4 * v3);
-    int32_t* d_id = (int32_t*)(buf + 4 * v3 + (size_t)n * sizeof(double));
-    hipError_t e = hipMemcpy(d_o, origins, v3, hipMemcpyHostToDevice);
+    const size_t v3 = (size_t)n * 3 * sizeof(double);
+    DeviceBlock buf;
+    const size_t at_o = buf.part(v3), at_d = buf.part(v3), at_pos = buf.part(v3), at_n = buf.part(v3);
+    const size_t at_t = buf.part((size_t)n * sizeof(double)), at_id = buf.part((size_t)n * sizeof(int32_t));
+    hipError_t e = buf.alloc();
+    if (e != hipSuccess) return oom_or_hip(e, "rt_trace_rays buffers");
+    double *d_o = buf.at<double>(at_o), *d_d = buf.at<double>(at_d), *d_pos = buf.at<double>(at_pos);
+    double *d_n = buf.at<double>(at_n), *d_t = buf.at<double>(at_t);
+    int32_t* d_id = buf.at<int32_t>(at_id);
+    e = hipMemcpy(d_o, origins, v3, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_d, dirs, v3, hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = rt::launch_trace_f64(ds, (long)n, d_o, d_d, d_t, d_id, d_pos, d_n, (flags & RT_FLAG_MESH_NEAREST) != 0, nullptr);
@@ -1512,7 +1601,6 @@ int rt_trace_rays_flags(const rt_scene* scene, int32_t device, uint32_t flags, i
     if (e == hipSuccess) e = hipMemcpy(object, d_id, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && pos) e = hipMemcpy(pos, d_pos, v3, hipMemcpyDeviceToHost);
     if (e == hipSuccess && normal) e = hipMemcpy(normal, d_n, v3, hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_trace_rays: ") + hipGetErrorString(e));
     return RT_OK;
 }
@@ -1614,32 +1702,79 @@ void scratch_give(int device, void* p, size_t bytes) {
     if (drop) (void)hipFree(drop);
 }
 
-// Enqueues the filter on `st` and waits for it, so its scratch is idle again when the call returns.
-int denoise_run(int32_t device, int32_t width, int32_t height, const double* d_sub, const float* d_feat,
-                int32_t levels, const float sigma[4], uint8_t* d_rgb, float* d_lin, hipStream_t st) {
+// The checks that open the four filter entry points (rt_denoise*: `var` is checked by the two that take one), and
+// the device selected.
+int denoise_begin(const char* who, int32_t device, int32_t width, int32_t height, const void* sub, const void* feat,
+                  int32_t levels, const float sigma[4], const void* rgb_out) {
+    int rc = check_denoise(who, width, height, sub, feat, levels, sigma, rgb_out);
+    if (rc == RT_OK) rc = need_device(who, device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    return RT_OK;
+}
+
+// Enqueues the filter on `st` and waits for it, so its scratch is idle again when the call returns. With d_var
+// (rt_denoise_var*) the variance-guided filter runs, and d_vout may ask for the filtered variance.
+int denoise_run(const char* who, int32_t device, int32_t width, int32_t height, const double* d_sub,
+                const float* d_feat, const float* d_var, int32_t levels, const float sigma[4], uint8_t* d_rgb,
+                float* d_lin, float* d_vout, hipStream_t st) {
     const long npix = (long)width * height;
     hipError_t e = hipSuccess;
     if (levels == 0) {
-        // the pass-through: rt_render's own RGB8 (k_finalize_f64), byte for byte
-        rt::RenderArgs a{};
-        a.tw = width;
-        a.th = height;
-        a.rgb_out = d_rgb;
-        e = rt::launch_finalize_f64(a, d_sub, st);
-        if (e == hipSuccess && !d_lin) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(RT_E_HIP, std::string("denoise: ") + hipGetErrorString(e));
-        if (!d_lin) return RT_OK;
+        // the pass-through: the RGB8 is rt_render's own; only a linear or a variance output still needs the filter
+        e = finalize_rgb(width, height, d_sub, d_rgb, st);
+        if (e == hipSuccess && !d_lin && !d_vout) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        if (!d_lin && !d_vout) return RT_OK;
     }
     const size_t bytes = rt::atrous_scratch_bytes(npix);
     void* scratch = scratch_take(device, bytes, &e);
-    if (!scratch)
-        return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, std::string("denoise scratch: ") + hipGetErrorString(e));
-    e = rt::launch_atrous(width, height, d_sub, d_feat, levels, sigma[0], sigma[1], sigma[2], sigma[3], scratch,
-                          levels == 0 ? nullptr : d_rgb, d_lin, st);
+    if (!scratch) return oom_or_hip(e, std::string(who) + " scratch");
+    uint8_t* rgb = levels == 0 ? nullptr : d_rgb;
+    e = d_var ? rt::launch_atrous_var(width, height, d_sub, d_feat, d_var, levels, sigma[0], sigma[1], sigma[2],
+                                      sigma[3], scratch, rgb, d_lin, d_vout, st)
+              : rt::launch_atrous(width, height, d_sub, d_feat, levels, sigma[0], sigma[1], sigma[2], sigma[3], scratch,
+                                  rgb, d_lin, st);
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
     scratch_give(device, scratch, bytes);
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("denoise: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// The host form of the filter (rt_denoise, and with `var` rt_denoise_var): uploads into one block, runs the filter on
+// a stream of the call's own, and copies back the outputs asked for. Arguments checked by denoise_begin.
+int denoise_host(const char* who, int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
+                 const float* var, int32_t levels, const float sigma[4], uint8_t* rgb_out, float* lin_out,
+                 float* var_out) {
+    const size_t npix = (size_t)width * height;
+    const size_t b_sub = npix * 12 * sizeof(double), b_feat = npix * rt::kFeatFloats * sizeof(float);
+    const size_t b_var = npix * 4 * sizeof(float), b_lin = npix * 3 * sizeof(float), b_vout = npix * sizeof(float);
+    DeviceBlock buf;
+    const size_t at_sub = buf.part(b_sub), at_feat = buf.part(b_feat), at_var = buf.part(var ? b_var : 0);
+    const size_t at_lin = buf.part(lin_out ? b_lin : 0), at_vout = buf.part(var_out ? b_vout : 0), at_rgb = buf.part(npix * 3);
+    hipError_t e = buf.alloc();
+    if (e != hipSuccess) return oom_or_hip(e, std::string(who) + " buffers");
+    double* d_sub = buf.at<double>(at_sub);
+    float* d_feat = buf.at<float>(at_feat);
+    float* d_var = var ? buf.at<float>(at_var) : nullptr;
+    float* d_lin = lin_out ? buf.at<float>(at_lin) : nullptr;
+    float* d_vout = var_out ? buf.at<float>(at_vout) : nullptr;
+    uint8_t* d_rgb = buf.at<uint8_t>(at_rgb);
+    CallStream cs;
+    e = cs.init();
+    if (e == hipSuccess) e = hipMemcpyAsync(d_sub, sub, b_sub, hipMemcpyHostToDevice, cs.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_feat, feat, b_feat, hipMemcpyHostToDevice, cs.st);
+    if (e == hipSuccess && var) e = hipMemcpyAsync(d_var, var, b_var, hipMemcpyHostToDevice, cs.st);
+    if (e == hipSuccess) {
+        const int rc = denoise_run(who, device, width, height, d_sub, d_feat, d_var, levels, sigma, d_rgb, d_lin, d_vout, cs.st);
+        if (rc != RT_OK) return rc;
+        e = hipMemcpyAsync(rgb_out, d_rgb, npix * 3, hipMemcpyDeviceToHost, cs.st);
+    }
+    if (e == hipSuccess && lin_out) e = hipMemcpyAsync(lin_out, d_lin, b_lin, hipMemcpyDeviceToHost, cs.st);
+    if (e == hipSuccess && var_out) e = hipMemcpyAsync(var_out, d_vout, b_vout, hipMemcpyDeviceToHost, cs.st);
+    if (e == hipSuccess) e = cs.close();
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
     return RT_OK;
 }
 
@@ -1659,70 +1794,35 @@ int rt_render_features(const rt_scene* scene, const rt_render_params* p, float* 
     const size_t bytes = (size_t)p->tile_w * p->tile_h * rt::kFeatFloats * sizeof(float);
     if (bytes == 0) return RT_OK;
     HIP_TRY(hipSetDevice(p->device));
-    float* d_feat = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_feat, bytes));
+    DeviceBlock buf;
+    buf.part(bytes);
+    hipError_t e = buf.alloc();
+    if (e != hipSuccess) return oom_or_hip(e, "rt_render_features buffer");
+    float* d_feat = buf.at<float>(0);
     rc = features_enqueue(const_cast<rt_scene*>(scene), p, d_feat, nullptr);
-    std::string err = g_err;
-    if (rc == RT_OK) {
-        hipError_t e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess) e = hipMemcpy(feat_out, d_feat, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_render_features: ") + hipGetErrorString(e); }
-    } else {
-        (void)hipStreamSynchronize(nullptr);
-    }
-    (void)hipFree(d_feat);
-    return rc < 0 ? fail(rc, err) : rc;
+    e = hipStreamSynchronize(nullptr);  // also after a failed enqueue: what it did enqueue is drained
+    if (rc != RT_OK) return rc;
+    if (e == hipSuccess) e = hipMemcpy(feat_out, d_feat, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_render_features: ") + hipGetErrorString(e));
+    return RT_OK;
 }
 
 int rt_denoise_device(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
                       int32_t levels, float sigma_c, float sigma_n, float sigma_z, float sigma_a, uint8_t* rgb_out,
                       float* lin_out, void* stream) {
     const float sigma[4] = {sigma_c, sigma_n, sigma_z, sigma_a};
-    int rc = check_denoise("rt_denoise_device", width, height, sub, feat, levels, sigma, rgb_out);
-    if (rc == RT_OK) rc = need_device("rt_denoise_device", device);
+    const int rc = denoise_begin("rt_denoise_device", device, width, height, sub, feat, levels, sigma, rgb_out);
     if (rc != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    return denoise_run(device, width, height, sub, feat, levels, sigma, rgb_out, lin_out, (hipStream_t)stream);
+    return denoise_run("rt_denoise_device", device, width, height, sub, feat, nullptr, levels, sigma, rgb_out, lin_out,
+                       nullptr, (hipStream_t)stream);
 }
 
 int rt_denoise(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat, int32_t levels,
                float sigma_c, float sigma_n, float sigma_z, float sigma_a, uint8_t* rgb_out, float* lin_out) {
     const float sigma[4] = {sigma_c, sigma_n, sigma_z, sigma_a};
-    int rc = check_denoise("rt_denoise", width, height, sub, feat, levels, sigma, rgb_out);
-    if (rc == RT_OK) rc = need_device("rt_denoise", device);
+    const int rc = denoise_begin("rt_denoise", device, width, height, sub, feat, levels, sigma, rgb_out);
     if (rc != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t npix = (size_t)width * height;
-    const size_t b_sub = npix * 12 * sizeof(double), b_feat = npix * rt::kFeatFloats * sizeof(float);
-    const size_t b_lin = npix * 3 * sizeof(float), b_rgb = align_up(npix * 3, 16);
-    // one allocation: sub | feat | lin | rgb (each part 16-byte aligned)
-    char* buf = nullptr;
-    hipError_t e = hipMalloc((void**)&buf, b_sub + b_feat + b_lin + b_rgb + 16);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, std::string("rt_denoise buffers: ") + hipGetErrorString(e));
-    double* d_sub = (double*)buf;
-    float* d_feat = (float*)(buf + b_sub);
-    float* d_lin = (float*)(buf + b_sub + b_feat);
-    uint8_t* d_rgb = (uint8_t*)(buf + align_up(b_sub + b_feat + b_lin, 16));
-    hipStream_t st = nullptr;
-    e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sub, sub, b_sub, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_feat, feat, b_feat, hipMemcpyHostToDevice, st);
-    std::string err;
-    if (e == hipSuccess) {
-        rc = denoise_run(device, width, height, d_sub, d_feat, levels, sigma, d_rgb, lin_out ? d_lin : nullptr, st);
-        err = g_err;
-    }
-    if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync(rgb_out, d_rgb, npix * 3, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && rc == RT_OK && lin_out) e = hipMemcpyAsync(lin_out, d_lin, b_lin, hipMemcpyDeviceToHost, st);
-    if (st) {
-        const hipError_t es = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = es;
-        (void)hipStreamDestroy(st);
-    }
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_denoise: ") + hipGetErrorString(e));
-    return rc < 0 ? fail(rc, err) : rc;
+    return denoise_host("rt_denoise", device, width, height, sub, feat, nullptr, levels, sigma, rgb_out, lin_out, nullptr);
 }
 
 // Progressive accumulation ----------------------------------------------------------------
@@ -1756,29 +1856,26 @@ struct rt_accum {
 
 namespace {
 
-int oom_or_hip(hipError_t e, const char* what) {
-    return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+// The accumulator's error-target buffers (DESIGN.md §13): cnt | list | selection scratch | total.
+// (the scratch and the total 16-byte aligned; the scratch holds 8-byte words)
+size_t adapt_scratch_at(const rt_accum* a) { return align_up(a->npix() * 12, 16); }
+size_t adapt_total_at(const rt_accum* a) {
+    return adapt_scratch_at(a) + align_up(rt::select_scratch_bytes((long)a->npix()), 16);
 }
+size_t adapt_bytes(const rt_accum* a) { return adapt_total_at(a) + 16; }
+uint32_t* adapt_list(const rt_accum* a) { return (uint32_t*)(a->adapt + a->npix() * 8); }
+void* adapt_scratch(const rt_accum* a) { return a->adapt + adapt_scratch_at(a); }
+uint32_t* adapt_total(const rt_accum* a) { return (uint32_t*)(a->adapt + adapt_total_at(a)); }
 
-// A stream for one call: waited for and destroyed when the call returns.
-struct CallStream {
-    hipStream_t st = nullptr;
-    CallStream() = default;
-    CallStream(const CallStream&) = delete;
-    CallStream& operator=(const CallStream&) = delete;
-    hipError_t init() { return hipStreamCreateWithFlags(&st, hipStreamNonBlocking); }
-    ~CallStream() {
-        if (!st) return;
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamDestroy(st);
-    }
-};
-
-// Selects the accumulator's device and makes what the call needs of its sums and staging area.
-int accum_ready(rt_accum* a, bool sums, bool stage) {
+// Makes the accumulator's device state ready for the entry point `who`, after its checks that need no device: the
+// ordinal names a visible device, which is selected; the sums exist, and what the call needs of the staging area
+// and of the error-target buffers.
+int accum_ready(const char* who, rt_accum* a, bool stage, bool adapt) {
+    const int rc = need_device(who, a->device);
+    if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(a->device));
     hipError_t e = hipSuccess;
-    if (sums && !a->S) {
+    if (!a->S) {
         e = hipMalloc((void**)&a->S, 2 * a->sub_bytes());
         if (e == hipSuccess) a->Q = a->S + a->npix() * 12;
         else a->S = nullptr;
@@ -1788,6 +1885,13 @@ int accum_ready(rt_accum* a, bool sums, bool stage) {
         if (e != hipSuccess) a->stage = nullptr;
     }
     if (e != hipSuccess) return oom_or_hip(e, "rt_accum buffers");
+    if (adapt && !a->adapt) {
+        e = hipMalloc((void**)&a->adapt, adapt_bytes(a));
+        if (e != hipSuccess) {
+            a->adapt = nullptr;
+            return oom_or_hip(e, "rt_accum error-target buffers");
+        }
+    }
     return RT_OK;
 }
 
@@ -1832,43 +1936,8 @@ int check_accum_resolve(const char* who, const rt_accum* a, const void* var) {
 hipError_t accum_resolve_enqueue(rt_accum* a, double* d_sub, float* d_var, uint8_t* d_rgb, hipStream_t st) {
     hipError_t e = a->sparse ? rt::launch_accum_resolve_cnt(a->S, a->Q, a->cnt(), (long)a->npix(), d_sub, d_var, st)
                              : rt::launch_accum_resolve(a->S, a->Q, (long)a->npix(), a->N, a->K, d_sub, d_var, st);
-    if (e == hipSuccess && d_rgb) {
-        rt::RenderArgs ra{};
-        ra.tw = a->width;
-        ra.th = a->height;
-        ra.rgb_out = d_rgb;
-        e = rt::launch_finalize_f64(ra, d_sub, st);
-    }
+    if (e == hipSuccess && d_rgb) e = finalize_rgb(a->width, a->height, d_sub, d_rgb, st);
     return e;
-}
-
-// rt_denoise_var*: denoise_run with the variance.
-int denoise_var_run(int32_t device, int32_t width, int32_t height, const double* d_sub, const float* d_feat,
-                    const float* d_var, int32_t levels, const float sigma[4], uint8_t* d_rgb, float* d_lin,
-                    float* d_vout, hipStream_t st) {
-    const long npix = (long)width * height;
-    hipError_t e = hipSuccess;
-    if (levels == 0) {
-        // the pass-through: rt_render's own RGB8 (k_finalize_f64), byte for byte
-        rt::RenderArgs a{};
-        a.tw = width;
-        a.th = height;
-        a.rgb_out = d_rgb;
-        e = rt::launch_finalize_f64(a, d_sub, st);
-        if (e == hipSuccess && !d_lin && !d_vout) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(RT_E_HIP, std::string("denoise_var: ") + hipGetErrorString(e));
-        if (!d_lin && !d_vout) return RT_OK;
-    }
-    const size_t bytes = rt::atrous_scratch_bytes(npix);
-    void* scratch = scratch_take(device, bytes, &e);
-    if (!scratch) return oom_or_hip(e, "denoise_var scratch");
-    e = rt::launch_atrous_var(width, height, d_sub, d_feat, d_var, levels, sigma[0], sigma[1], sigma[2], sigma[3],
-                              scratch, levels == 0 ? nullptr : d_rgb, d_lin, d_vout, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    scratch_give(device, scratch, bytes);
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("denoise_var: ") + hipGetErrorString(e));
-    return RT_OK;
 }
 
 }  // namespace
@@ -1924,42 +1993,22 @@ int rt_accum_add(void* accum, const rt_scene* scene, const rt_render_params* p, 
                  rt_render_stats* stats) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_accum_add(a, scene, p);
-    if (rc == RT_OK) rc = need_device("rt_accum_add", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_add", a, true, false);
     if (rc != RT_OK) return rc;
-    CallStream cs;  // destroyed last: after the stats' events and the cancel word have gone back
-    hipError_t ce = cs.init();
-    CancelMirror mirror;
-    if (ce == hipSuccess && cancel) ce = mirror.init();
-    if (ce != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_add: ") + hipGetErrorString(ce));
-    rt_render_stats local;
-    PendingStats ps;
-    ps.out = stats ? stats : &local;
-    hipStream_t st = cs.st;
-    rc = render_enqueue(const_cast<rt_scene*>(scene), p, a->stage_rgb(), a->stage_sub(), st, mirror.dev, cancel, &ps);
-    std::string err = g_err;
-    if (rc == RT_OK) {
-        // as rt_render: wait for the render while relaying the cancel flag
-        const hipError_t e = wait_stream(st, cancel, &mirror);
-        if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_accum_add: ") + hipGetErrorString(e); }
-        if (rc == RT_OK) {
-            const int f = ps.finish(&err);
-            if (f < 0) rc = f;
-        }
-        if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
-    } else {
-        (void)hipStreamSynchronize(st);
-    }
-    if (rc < 0) return fail(rc, err);
-    if (rc != RT_OK) return rc;  // cancelled: S, Q, K and N untouched
-    return accum_merge(a, a->stage_sub(), p->spp / 4, st);
+    RenderCall call;
+    rc = call.init("rt_accum_add", cancel, stats);
+    if (rc != RT_OK) return rc;
+    rc = render_enqueue(const_cast<rt_scene*>(scene), p, a->stage_rgb(), a->stage_sub(), call.cs.st, call.mirror.dev,
+                        cancel, &call.ps);
+    rc = call.finish("rt_accum_add", rc);
+    if (rc != RT_OK) return rc;  // failed, or cancelled: S, Q, K and N untouched
+    return accum_merge(a, a->stage_sub(), p->spp / 4, call.cs.st);
 }
 
 int rt_accum_add_sub(void* accum, const double* sub, int32_t n) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_accum_sub("rt_accum_add_sub", a, sub, n);
-    if (rc == RT_OK) rc = need_device("rt_accum_add_sub", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_add_sub", a, true, false);
     if (rc != RT_OK) return rc;
     CallStream cs;
     HIP_TRY(cs.init());
@@ -1970,8 +2019,7 @@ int rt_accum_add_sub(void* accum, const double* sub, int32_t n) {
 int rt_accum_add_sub_device(void* accum, const void* d_sub, int32_t n, void* stream) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_accum_sub("rt_accum_add_sub_device", a, d_sub, n);
-    if (rc == RT_OK) rc = need_device("rt_accum_add_sub_device", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, false);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_add_sub_device", a, false, false);
     if (rc != RT_OK) return rc;
     return accum_merge(a, (const double*)d_sub, n, (hipStream_t)stream);
 }
@@ -1979,9 +2027,8 @@ int rt_accum_add_sub_device(void* accum, const void* d_sub, int32_t n, void* str
 int rt_accum_resolve_device(void* accum, void* d_sub, void* d_var, void* d_rgb, void* stream) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_accum_resolve("rt_accum_resolve_device", a, d_var);
-    if (rc == RT_OK) rc = need_device("rt_accum_resolve_device", a->device);
     const bool stage = d_rgb && !d_sub;
-    if (rc == RT_OK) rc = accum_ready(a, true, stage);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_resolve_device", a, stage, false);
     if (rc != RT_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = accum_resolve_enqueue(a, stage ? a->stage_sub() : (double*)d_sub, (float*)d_var, (uint8_t*)d_rgb, st);
@@ -1994,8 +2041,7 @@ int rt_accum_resolve_device(void* accum, void* d_sub, void* d_var, void* d_rgb, 
 int rt_accum_resolve(void* accum, double* sub_out, float* var_out, uint8_t* rgb_out) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_accum_resolve("rt_accum_resolve", a, var_out);
-    if (rc == RT_OK) rc = need_device("rt_accum_resolve", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, true);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_resolve", a, true, false);
     if (rc != RT_OK) return rc;
     CallStream cs;
     HIP_TRY(cs.init());
@@ -2018,12 +2064,10 @@ int rt_denoise_var_device(int32_t device, int32_t width, int32_t height, const d
                           float sigma_a, uint8_t* rgb_out, float* lin_out, float* var_out, void* stream) {
     const float sigma[4] = {sigma_c, sigma_n, sigma_z, sigma_a};
     if (!var) return fail(RT_E_INVAL, "rt_denoise_var_device: null argument");
-    int rc = check_denoise("rt_denoise_var_device", width, height, sub, feat, levels, sigma, rgb_out);
-    if (rc == RT_OK) rc = need_device("rt_denoise_var_device", device);
+    const int rc = denoise_begin("rt_denoise_var_device", device, width, height, sub, feat, levels, sigma, rgb_out);
     if (rc != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    return denoise_var_run(device, width, height, sub, feat, var, levels, sigma, rgb_out, lin_out, var_out,
-                           (hipStream_t)stream);
+    return denoise_run("rt_denoise_var_device", device, width, height, sub, feat, var, levels, sigma, rgb_out, lin_out,
+                       var_out, (hipStream_t)stream);
 }
 
 int rt_denoise_var(int32_t device, int32_t width, int32_t height, const double* sub, const float* feat,
@@ -2031,48 +2075,9 @@ int rt_denoise_var(int32_t device, int32_t width, int32_t height, const double* 
                    uint8_t* rgb_out, float* lin_out, float* var_out) {
     const float sigma[4] = {sigma_c, sigma_n, sigma_z, sigma_a};
     if (!var) return fail(RT_E_INVAL, "rt_denoise_var: null argument");
-    int rc = check_denoise("rt_denoise_var", width, height, sub, feat, levels, sigma, rgb_out);
-    if (rc == RT_OK) rc = need_device("rt_denoise_var", device);
+    const int rc = denoise_begin("rt_denoise_var", device, width, height, sub, feat, levels, sigma, rgb_out);
     if (rc != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t npix = (size_t)width * height;
-    const size_t b_sub = npix * 12 * sizeof(double), b_feat = npix * rt::kFeatFloats * sizeof(float);
-    const size_t b_var = npix * 4 * sizeof(float), b_lin = align_up(npix * 3 * sizeof(float), 16);
-    const size_t b_vout = align_up(npix * sizeof(float), 16), b_rgb = align_up(npix * 3, 16);
-    // one allocation: sub | feat | var | lin | vout | rgb (each part 16-byte aligned)
-    char* buf = nullptr;
-    hipError_t e = hipMalloc((void**)&buf, b_sub + b_feat + b_var + b_lin + b_vout + b_rgb);
-    if (e != hipSuccess) return oom_or_hip(e, "rt_denoise_var buffers");
-    double* d_sub = (double*)buf;
-    float* d_feat = (float*)(buf + b_sub);
-    float* d_var = (float*)(buf + b_sub + b_feat);
-    float* d_lin = (float*)(buf + b_sub + b_feat + b_var);
-    float* d_vout = (float*)(buf + b_sub + b_feat + b_var + b_lin);
-    uint8_t* d_rgb = (uint8_t*)(buf + b_sub + b_feat + b_var + b_lin + b_vout);
-    hipStream_t st = nullptr;
-    e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sub, sub, b_sub, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_feat, feat, b_feat, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_var, var, b_var, hipMemcpyHostToDevice, st);
-    std::string err;
-    if (e == hipSuccess) {
-        rc = denoise_var_run(device, width, height, d_sub, d_feat, d_var, levels, sigma, d_rgb, lin_out ? d_lin : nullptr,
-                             var_out ? d_vout : nullptr, st);
-        err = g_err;
-    }
-    if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync(rgb_out, d_rgb, npix * 3, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && rc == RT_OK && lin_out)
-        e = hipMemcpyAsync(lin_out, d_lin, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && rc == RT_OK && var_out)
-        e = hipMemcpyAsync(var_out, d_vout, npix * sizeof(float), hipMemcpyDeviceToHost, st);
-    if (st) {
-        const hipError_t es = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = es;
-        (void)hipStreamDestroy(st);
-    }
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_denoise_var: ") + hipGetErrorString(e));
-    return rc < 0 ? fail(rc, err) : rc;
+    return denoise_host("rt_denoise_var", device, width, height, sub, feat, var, levels, sigma, rgb_out, lin_out, var_out);
 }
 
 // Rendering to a per-pixel error target ---------------------------------------------------
@@ -2155,26 +2160,6 @@ int render_pixels_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t
     return RT_OK;
 }
 
-// The accumulator's error-target buffers: cnt | list | selection scratch | total.
-// (the scratch and the total 16-byte aligned; the scratch holds 8-byte words)
-size_t adapt_scratch_at(const rt_accum* a) { return align_up(a->npix() * 12, 16); }
-size_t adapt_total_at(const rt_accum* a) {
-    return adapt_scratch_at(a) + align_up(rt::select_scratch_bytes((long)a->npix()), 16);
-}
-size_t adapt_bytes(const rt_accum* a) { return adapt_total_at(a) + 16; }
-uint32_t* adapt_list(const rt_accum* a) { return (uint32_t*)(a->adapt + a->npix() * 8); }
-void* adapt_scratch(const rt_accum* a) { return a->adapt + adapt_scratch_at(a); }
-uint32_t* adapt_total(const rt_accum* a) { return (uint32_t*)(a->adapt + adapt_total_at(a)); }
-int adapt_ready(rt_accum* a) {
-    if (a->adapt) return RT_OK;
-    const hipError_t e = hipMalloc((void**)&a->adapt, adapt_bytes(a));
-    if (e != hipSuccess) {
-        a->adapt = nullptr;
-        return oom_or_hip(e, "rt_accum error-target buffers");
-    }
-    return RT_OK;
-}
-
 // host_list: the list is on the host and checked (strictly ascending ids below width * height).
 int check_sparse(const char* who, const rt_accum* a, const void* pixels, int64_t n_pixels, bool host_list) {
     const std::string w(who);
@@ -2213,6 +2198,37 @@ int check_select(const char* who, const rt_accum* a, float abs_tol, float rel_to
     return RT_OK;
 }
 
+// The end of a compaction into a pixel list (select_run, holes_run), enqueued on `st` with outcome e: waits, and
+// reads the list's full length from adapt_total and, where asked, the 8-byte count the kernel left at d_extra.
+int list_counts(const char* who, rt_accum* a, hipError_t e, hipStream_t st, int64_t* n_out,
+                const unsigned long long* d_extra = nullptr, int64_t* extra_out = nullptr) {
+    uint32_t total = 0;
+    unsigned long long extra = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, adapt_total(a), sizeof total, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && extra_out) e = hipMemcpyAsync(&extra, d_extra, sizeof extra, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    *n_out = (int64_t)total;
+    if (extra_out) *extra_out = (int64_t)extra;
+    return RT_OK;
+}
+
+// The host form of a compaction (rt_accum_select, rt_accum_holes): run(d_list, cap, st) compacts into the
+// accumulator's own list buffer on a stream of the call's and leaves the full length in *n_out; the first
+// min(*n_out, cap) ids go back to the caller.
+int list_to_host(rt_accum* a, uint32_t* pixels_out, int64_t cap, const int64_t* n_out,
+                 const std::function<int(uint32_t*, int64_t, hipStream_t)>& run) {
+    CallStream cs;
+    HIP_TRY(cs.init());
+    const int64_t dcap = std::min<int64_t>(cap, (int64_t)a->npix());  // the list buffer holds every pixel
+    const int rc = run(adapt_list(a), dcap, cs.st);
+    if (rc != RT_OK) return rc;
+    const int64_t n = std::min(*n_out, dcap);
+    if (n > 0) HIP_TRY(hipMemcpy(pixels_out, adapt_list(a), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 // Resolves the variance into the staging area, selects into d_out (device, cap ids) on `st`, waits, and reads the count.
 int select_run(rt_accum* a, float abs_tol, float rel_tol, int32_t max_n, uint32_t* d_out, int64_t cap, int64_t* n_out,
                hipStream_t st) {
@@ -2220,13 +2236,7 @@ int select_run(rt_accum* a, float abs_tol, float rel_tol, int32_t max_n, uint32_
     if (e == hipSuccess)
         e = rt::launch_accum_select(a->S, a->stage_var(), a->sparse ? a->cnt() : nullptr, a->N, a->width, a->height,
                                     abs_tol, rel_tol, max_n, adapt_scratch(a), d_out, (long)cap, adapt_total(a), st);
-    uint32_t total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, adapt_total(a), sizeof total, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_select: ") + hipGetErrorString(e));
-    *n_out = (int64_t)total;
-    return RT_OK;
+    return list_counts("rt_accum_select", a, e, st, n_out);
 }
 
 }  // namespace
@@ -2246,12 +2256,7 @@ int rt_render_pixels_device(const rt_scene* scene, const rt_render_params* param
     ps.out = stats;
     rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), params, (const uint32_t*)d_pixels, n_pixels, (uint8_t*)d_rgb,
                                (double*)d_sub, st, nullptr, stats ? &ps : nullptr);
-    if (rc < 0 || !stats) return rc;
-    const hipError_t e = hipStreamSynchronize(st);  // stats: synchronous with respect to the stream (rt_ffi.h)
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("stats sync: ") + hipGetErrorString(e));
-    std::string err;
-    const int f = ps.finish(&err);
-    return f < 0 ? fail(f, err) : rc;
+    return stats_sync(rc, st, stats ? &ps : nullptr);
 }
 
 int rt_render_pixels(const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels, int64_t n_pixels,
@@ -2266,51 +2271,19 @@ int rt_render_pixels(const rt_scene* scene, const rt_render_params* p, const uin
     rc = need_device("rt_render_pixels", p->device);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
-    const size_t n = (size_t)n_pixels;
-    const size_t b_sub = n * 12 * sizeof(double), b_pix = align_up(n * sizeof(uint32_t), 16);
-    // one allocation: sub | pixels | rgb (each part 16-byte aligned)
-    char* buf = nullptr;
-    hipError_t e = hipMalloc((void**)&buf, b_sub + b_pix + align_up(n * 3, 16));
-    if (e != hipSuccess) return oom_or_hip(e, "rt_render_pixels buffers");
-    double* d_sub = (double*)buf;
-    uint32_t* d_pix = (uint32_t*)(buf + b_sub);
-    uint8_t* d_rgb = (uint8_t*)(buf + b_sub + b_pix);
-    std::string err;
-    {
-        CallStream cs;  // waited for and destroyed before the buffers are freed
-        CancelMirror mirror;
-        e = cs.init();
-        if (e == hipSuccess && cancel) e = mirror.init();
-        hipStream_t st = cs.st;
-        if (e == hipSuccess) e = hipMemcpyAsync(d_pix, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) {
-            rc = RT_E_HIP;
-            err = std::string("rt_render_pixels: ") + hipGetErrorString(e);
-        }
-        rt_render_stats local;
-        PendingStats ps;
-        ps.out = stats ? stats : &local;
-        if (rc == RT_OK) {
-            rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), p, d_pix, n_pixels, rgb_out ? d_rgb : nullptr, d_sub, st,
-                                       mirror.dev, &ps);
-            err = g_err;
-        }
-        if (rc == RT_OK) {
-            // as rt_render: wait for the render while relaying the cancel flag, then copy back
-            e = wait_stream(st, cancel, &mirror);
-            if (e == hipSuccess && rgb_out) e = hipMemcpyAsync(rgb_out, d_rgb, n * 3, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && sub_out) e = hipMemcpyAsync(sub_out, d_sub, b_sub, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_render_pixels readback: ") + hipGetErrorString(e); }
-            if (rc == RT_OK) {
-                const int f = ps.finish(&err);
-                if (f < 0) rc = f;
-            }
-            if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
-        }
-    }
-    (void)hipFree(buf);
-    return rc < 0 ? fail(rc, err) : rc;
+    const size_t n = (size_t)n_pixels, b_sub = n * 12 * sizeof(double);
+    RenderCall call;
+    const size_t at_sub = call.mem.part(b_sub), at_pix = call.mem.part(n * sizeof(uint32_t)), at_rgb = call.mem.part(n * 3);
+    rc = call.init("rt_render_pixels", cancel, stats);
+    if (rc != RT_OK) return rc;
+    double* d_sub = call.mem.at<double>(at_sub);
+    uint32_t* d_pix = call.mem.at<uint32_t>(at_pix);
+    uint8_t* d_rgb = call.mem.at<uint8_t>(at_rgb);
+    const hipError_t e = hipMemcpyAsync(d_pix, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, call.cs.st);
+    if (e != hipSuccess) return oom_or_hip(e, "rt_render_pixels");
+    rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), p, d_pix, n_pixels, rgb_out ? d_rgb : nullptr, d_sub,
+                               call.cs.st, call.mirror.dev, &call.ps);
+    return call.finish("rt_render_pixels", rc, {{rgb_out, d_rgb, n * 3}, {sub_out, d_sub, b_sub}});
 }
 
 int rt_accum_add_pixels(void* accum, const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels,
@@ -2324,36 +2297,18 @@ int rt_accum_add_pixels(void* accum, const rt_scene* scene, const rt_render_para
         if (stats) std::memset(stats, 0, sizeof *stats);
         return RT_OK;
     }
-    rc = need_device("rt_accum_add_pixels", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, true);
-    if (rc == RT_OK) rc = adapt_ready(a);
+    rc = accum_ready("rt_accum_add_pixels", a, true, true);
     if (rc != RT_OK) return rc;
-    CallStream cs;  // destroyed last: after the stats' events and the cancel word have gone back
-    hipError_t ce = cs.init();
-    CancelMirror mirror;
-    if (ce == hipSuccess && cancel) ce = mirror.init();
-    hipStream_t st = cs.st;
-    if (ce == hipSuccess) ce = hipMemcpyAsync(adapt_list(a), pixels, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-    if (ce != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_add_pixels: ") + hipGetErrorString(ce));
-    rt_render_stats local;
-    PendingStats ps;
-    ps.out = stats ? stats : &local;
+    RenderCall call;
+    rc = call.init("rt_accum_add_pixels", cancel, stats);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = call.cs.st;
+    const hipError_t e = hipMemcpyAsync(adapt_list(a), pixels, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return oom_or_hip(e, "rt_accum_add_pixels");
     rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), p, adapt_list(a), n_pixels, nullptr, a->stage_sub(), st,
-                               mirror.dev, &ps);
-    std::string err = g_err;
-    if (rc == RT_OK) {
-        const hipError_t e = wait_stream(st, cancel, &mirror);
-        if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_accum_add_pixels: ") + hipGetErrorString(e); }
-        if (rc == RT_OK) {
-            const int f = ps.finish(&err);
-            if (f < 0) rc = f;
-        }
-        if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
-    } else {
-        (void)hipStreamSynchronize(st);
-    }
-    if (rc < 0) return fail(rc, err);
-    if (rc != RT_OK) return rc;  // cancelled: nothing merged
+                               call.mirror.dev, &call.ps);
+    rc = call.finish("rt_accum_add_pixels", rc);
+    if (rc != RT_OK) return rc;  // failed, or cancelled: nothing merged
     return accum_merge_list(a, adapt_list(a), n_pixels, a->stage_sub(), p->spp / 4, st);
 }
 
@@ -2364,9 +2319,7 @@ int rt_accum_add_sub_pixels(void* accum, const uint32_t* pixels, int64_t n_pixel
     if (rc == RT_OK && n_pixels > 0 && !sub) rc = fail(RT_E_INVAL, "rt_accum_add_sub_pixels: null argument");
     if (rc == RT_OK) rc = check_sparse("rt_accum_add_sub_pixels", a, pixels, n_pixels, true);
     if (rc != RT_OK || n_pixels == 0) return rc;
-    rc = need_device("rt_accum_add_sub_pixels", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, true);
-    if (rc == RT_OK) rc = adapt_ready(a);
+    rc = accum_ready("rt_accum_add_sub_pixels", a, true, true);
     if (rc != RT_OK) return rc;
     CallStream cs;
     HIP_TRY(cs.init());
@@ -2383,9 +2336,7 @@ int rt_accum_add_sub_pixels_device(void* accum, const void* d_pixels, int64_t n_
     if (rc == RT_OK && n_pixels > 0 && !d_sub) rc = fail(RT_E_INVAL, "rt_accum_add_sub_pixels_device: null argument");
     if (rc == RT_OK) rc = check_sparse("rt_accum_add_sub_pixels_device", a, d_pixels, n_pixels, false);
     if (rc != RT_OK || n_pixels == 0) return rc;
-    rc = need_device("rt_accum_add_sub_pixels_device", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, false);
-    if (rc == RT_OK) rc = adapt_ready(a);
+    rc = accum_ready("rt_accum_add_sub_pixels_device", a, false, true);
     if (rc != RT_OK) return rc;
     return accum_merge_list(a, (const uint32_t*)d_pixels, n_pixels, (const double*)d_sub, n, (hipStream_t)stream);
 }
@@ -2417,9 +2368,7 @@ int rt_accum_select_device(void* accum, float abs_tol, float rel_tol, int32_t ma
                            int64_t* n_out, void* stream) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_select("rt_accum_select_device", a, abs_tol, rel_tol, cap, d_pixels, n_out);
-    if (rc == RT_OK) rc = need_device("rt_accum_select_device", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, true);
-    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_select_device", a, true, true);
     if (rc != RT_OK) return rc;
     return select_run(a, abs_tol, rel_tol, max_n, (uint32_t*)d_pixels, cap, n_out, (hipStream_t)stream);
 }
@@ -2428,18 +2377,11 @@ int rt_accum_select(void* accum, float abs_tol, float rel_tol, int32_t max_n, ui
                     int64_t* n_out) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_select("rt_accum_select", a, abs_tol, rel_tol, cap, pixels_out, n_out);
-    if (rc == RT_OK) rc = need_device("rt_accum_select", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, true);
-    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_select", a, true, true);
     if (rc != RT_OK) return rc;
-    CallStream cs;
-    HIP_TRY(cs.init());
-    const int64_t dcap = std::min<int64_t>(cap, (int64_t)a->npix());  // the list buffer holds every pixel
-    rc = select_run(a, abs_tol, rel_tol, max_n, adapt_list(a), dcap, n_out, cs.st);
-    if (rc != RT_OK) return rc;
-    const int64_t n = std::min(*n_out, dcap);
-    if (n > 0) HIP_TRY(hipMemcpy(pixels_out, adapt_list(a), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return list_to_host(a, pixels_out, cap, n_out, [&](uint32_t* d_list, int64_t dcap, hipStream_t st) {
+        return select_run(a, abs_tol, rel_tol, max_n, d_list, dcap, n_out, st);
+    });
 }
 
 // Accumulator reprojection across camera moves ---------------------------------------------
@@ -2457,9 +2399,7 @@ int rt_accum_reproject(void* dst, void* src, const rt_scene* dst_view, const rt_
     if (flags & ~RT_FLAG_MESH_NEAREST) return fail(RT_E_INVAL, "rt_accum_reproject: unknown flag");
     if (s->K < 2 && !s->covered)
         return fail(RT_E_INVAL, "rt_accum_reproject: src needs at least two full-frame passes");
-    int rc = need_device("rt_accum_reproject", d->device);
-    if (rc == RT_OK) rc = accum_ready(d, true, false);
-    if (rc == RT_OK) rc = adapt_ready(d);
+    int rc = accum_ready("rt_accum_reproject", d, false, true);
     if (rc != RT_OK) return rc;
     rt::DevScene ds;
     rc = upload(const_cast<rt_scene*>(dst_view), d->device, &ds);  // the dst view's camera rides in ds
@@ -2543,16 +2483,7 @@ int holes_run(rt_accum* a, int32_t period, int32_t phase, uint32_t* d_out, int64
     unsigned long long* d_holes = (unsigned long long*)(adapt_total(a) + 2);
     hipError_t e = rt::launch_accum_holes(a->cnt(), a->width, a->height, period, phase, adapt_scratch(a), d_out, (long)cap,
                                           adapt_total(a), d_holes, st);
-    uint32_t total = 0;
-    unsigned long long holes = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, adapt_total(a), sizeof total, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&holes, d_holes, sizeof holes, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_holes: ") + hipGetErrorString(e));
-    *n_out = (int64_t)total;
-    if (n_holes) *n_holes = (int64_t)holes;
-    return RT_OK;
+    return list_counts("rt_accum_holes", a, e, st, n_out, d_holes, n_holes);
 }
 
 int check_holes_call(const char* who, const rt_accum* a, int32_t period, int32_t phase, int64_t cap, const void* out,
@@ -2569,9 +2500,7 @@ int rt_accum_holes_device(void* accum, int32_t period, int32_t phase, void* d_pi
                           int64_t* n_holes, void* stream) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_holes_call("rt_accum_holes_device", a, period, phase, cap, d_pixels, n_out);
-    if (rc == RT_OK) rc = need_device("rt_accum_holes_device", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, false);
-    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_holes_device", a, false, true);
     if (rc != RT_OK) return rc;
     return holes_run(a, period, phase, (uint32_t*)d_pixels, cap, n_out, n_holes, (hipStream_t)stream);
 }
@@ -2580,18 +2509,11 @@ int rt_accum_holes(void* accum, int32_t period, int32_t phase, uint32_t* pixels_
                    int64_t* n_holes) {
     rt_accum* a = (rt_accum*)accum;
     int rc = check_holes_call("rt_accum_holes", a, period, phase, cap, pixels_out, n_out);
-    if (rc == RT_OK) rc = need_device("rt_accum_holes", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, false);
-    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_holes", a, false, true);
     if (rc != RT_OK) return rc;
-    CallStream cs;
-    HIP_TRY(cs.init());
-    const int64_t dcap = std::min<int64_t>(cap, (int64_t)a->npix());  // the list buffer holds every pixel
-    rc = holes_run(a, period, phase, adapt_list(a), dcap, n_out, n_holes, cs.st);
-    if (rc != RT_OK) return rc;
-    const int64_t n = std::min(*n_out, dcap);
-    if (n > 0) HIP_TRY(hipMemcpy(pixels_out, adapt_list(a), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return list_to_host(a, pixels_out, cap, n_out, [&](uint32_t* d_list, int64_t dcap, hipStream_t st) {
+        return holes_run(a, period, phase, d_list, dcap, n_out, n_holes, st);
+    });
 }
 
 int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* p, uint64_t seed2, int32_t period,
@@ -2600,19 +2522,14 @@ int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* p,
     int rc = check_accum_add(a, scene, p);
     if (rc == RT_OK) rc = check_render_pixels("rt_accum_fill", scene, p, nullptr, 0);
     if (rc == RT_OK) rc = check_holes("rt_accum_fill", a, period, phase);
-    if (rc == RT_OK) rc = need_device("rt_accum_fill", a->device);
-    if (rc == RT_OK) rc = accum_ready(a, true, true);
-    if (rc == RT_OK) rc = adapt_ready(a);
+    if (rc == RT_OK) rc = accum_ready("rt_accum_fill", a, true, true);
     if (rc != RT_OK) return rc;
-    CallStream cs;  // destroyed last: after the stats' events and the cancel word have gone back
-    hipError_t ce = cs.init();
-    CancelMirror mirror;
-    if (ce == hipSuccess && cancel) ce = mirror.init();
-    if (ce != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum_fill: ") + hipGetErrorString(ce));
-    hipStream_t st = cs.st;
-    rt_render_stats sum, one;
+    rt_render_stats sum, one;  // each pass's stats go to `one`
     std::memset(&sum, 0, sizeof sum);
-    PendingStats ps;
+    RenderCall call;
+    rc = call.init("rt_accum_fill", cancel, &one);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = call.cs.st;
     int64_t lens[2] = {0, 0};
     for (int pass = 0; pass < 2; ++pass) {
         // pass 1: the holes and the refresh pattern; pass 2: what still lacks a second pass. The list stays on the
@@ -2626,22 +2543,10 @@ int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* p,
         if (n_list > (int64_t)INT32_MAX / 4) return fail(RT_E_INVAL, "rt_accum_fill: the list's length * 4 must fit an int32");
         rt_render_params pp = *p;
         if (pass == 1) pp.seed = seed2;
-        ps.out = &one;
         rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), &pp, adapt_list(a), n_list, nullptr, a->stage_sub(), st,
-                                   mirror.dev, &ps);
-        std::string err = g_err;
-        if (rc == RT_OK) {
-            const hipError_t e = wait_stream(st, cancel, &mirror);
-            if (e != hipSuccess) { rc = RT_E_HIP; err = std::string("rt_accum_fill: ") + hipGetErrorString(e); }
-            if (rc == RT_OK) {
-                const int f = ps.finish(&err);
-                if (f < 0) rc = f;
-            }
-            if (rc == RT_OK && cancel && *cancel) rc = RT_CANCELLED;
-        } else {
-            (void)hipStreamSynchronize(st);
-        }
-        if (rc < 0) return fail(rc, err);
+                                   call.mirror.dev, &call.ps);
+        rc = call.finish("rt_accum_fill", rc);
+        if (rc < 0) return rc;
         if (rc != RT_OK) break;  // cancelled: this pass merges nothing and the accumulator stays uncovered
         rc = accum_merge_list(a, adapt_list(a), n_list, a->stage_sub(), p->spp / 4, st);
         if (rc != RT_OK) return rc;
@@ -2710,20 +2615,18 @@ int diag_run(const char* who, const rt_scene* scene, int32_t device, int32_t for
     int rc = upload(const_cast<rt_scene*>(scene), device, &ds);
     if (rc != RT_OK) return rc;
     const size_t n = (size_t)a.n, v3 = n * 3 * sizeof(double);
-    size_t total = 2 * v3;
-    for (int k = 0; k < n_outs; ++k) total += align_up(outs[k].host ? n * outs[k].per : 0, 16);
-    char* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, total));
-    *d_in0 = (const double*)buf;
-    *d_in1 = (const double*)(buf + v3);
-    size_t off = 2 * v3;
-    for (int k = 0; k < n_outs; ++k) {
-        *outs[k].dev = outs[k].host ? (void*)(buf + off) : nullptr;
-        off += align_up(outs[k].host ? n * outs[k].per : 0, 16);
-    }
-    hipError_t e = hipMemcpy(buf, in0, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(buf + v3, in1, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(buf + 2 * v3, 0, total - 2 * v3);
+    DeviceBlock buf;
+    const size_t at_in0 = buf.part(v3), at_in1 = buf.part(v3), at_outs = buf.bytes;
+    size_t at[8];  // n_outs <= 5
+    for (int k = 0; k < n_outs; ++k) at[k] = buf.part(outs[k].host ? n * outs[k].per : 0);
+    hipError_t e = buf.alloc();
+    if (e != hipSuccess) return oom_or_hip(e, std::string(who) + " buffers");
+    *d_in0 = buf.at<const double>(at_in0);
+    *d_in1 = buf.at<const double>(at_in1);
+    for (int k = 0; k < n_outs; ++k) *outs[k].dev = outs[k].host ? buf.at<void>(at[k]) : nullptr;
+    e = hipMemcpy(buf.at<void>(at_in0), in0, v3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf.at<void>(at_in1), in1, v3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(buf.at<void>(at_outs), 0, buf.bytes - at_outs);
     if (e == hipSuccess) {
         if (form == RT_DIAG_FUSED || form == RT_DIAG_FUSED_G0 || form == RT_DIAG_FUSED_G1)
             e = rt::launch_diag_fused(ds, a, visible, form == RT_DIAG_FUSED_G0 ? 1 : form == RT_DIAG_FUSED_G1 ? 2 : 0,
@@ -2735,7 +2638,6 @@ int diag_run(const char* who, const rt_scene* scene, int32_t device, int32_t for
     if (e == hipSuccess) e = hipDeviceSynchronize();
     for (int k = 0; k < n_outs && e == hipSuccess; ++k)
         if (outs[k].host) e = hipMemcpy(outs[k].host, *outs[k].dev, n * outs[k].per, hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
     return RT_OK;
 }
