@@ -51,6 +51,15 @@ pub const RT_FLAG_FP32: u32 = 1 << 2;
 /// `Mesh::intersect` without the octree (src/geometry.rs:886-903), a BVH on the device.
 pub const RT_FLAG_MESH_NEAREST: u32 = 1 << 3;
 
+/// The kernel family of a pixel-list render (`rt_render_pixels_with`, `rt_render_pixels_path`).
+pub const RT_LIST_AUTO: i32 = 0;
+/// `k_render_list_f64`, the fused per-lane walk.
+pub const RT_LIST_FUSED: i32 = 1;
+/// The flat-octree query pool's list instance.
+pub const RT_LIST_FPOOL: i32 = 2;
+/// The role-split pool's list instance.
+pub const RT_LIST_ROLES: i32 = 3;
+
 pub const RT_BRDF_DIFFUSE: i32 = 0;
 pub const RT_BRDF_SPECULAR: i32 = 1;
 pub const RT_BRDF_PHONG: i32 = 2;
@@ -248,6 +257,21 @@ extern "C" {
     /// The same with device buffers, enqueued on `stream`; the list is the caller's contract.
     pub fn rt_render_pixels_device(
         scene: *const RtScene, params: *const RtRenderParams, d_pixels: *const c_void, n_pixels: i64,
+        d_rgb: *mut c_void, d_sub: *mut c_void, stream: *mut c_void, stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// `path_out[0]`: the kernel family (`RT_LIST_*`) `rt_render_pixels` takes for a list of `n_pixels`;
+    /// `path_out[1]`: the pool family the scene has under these flags (`RT_LIST_FUSED`: none). No GPU needed.
+    pub fn rt_render_pixels_path(
+        scene: *const RtScene, params: *const RtRenderParams, n_pixels: i64, path_out: *mut i32,
+    ) -> c_int;
+    /// `rt_render_pixels` with the kernel family chosen by the caller (`RT_LIST_AUTO`: `rt_render_pixels` itself);
+    /// a family the scene has no instance of is `RT_E_INVAL`. Same bits whichever family runs.
+    pub fn rt_render_pixels_with(
+        scene: *const RtScene, params: *const RtRenderParams, pixels: *const u32, n_pixels: i64, path: i32,
+        rgb_out: *mut u8, sub_out: *mut f64, cancel: *const i32, stats: *mut RtRenderStats,
+    ) -> c_int;
+    pub fn rt_render_pixels_with_device(
+        scene: *const RtScene, params: *const RtRenderParams, d_pixels: *const c_void, n_pixels: i64, path: i32,
         d_rgb: *mut c_void, d_sub: *mut c_void, stream: *mut c_void, stats: *mut RtRenderStats,
     ) -> c_int;
     /// Renders the listed pixels and merges them (needs two full-frame passes first); `RT_CANCELLED` merges nothing.

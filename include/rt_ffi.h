@@ -18,6 +18,8 @@
  *                          a filter guided by it)
  *   rt_render_pixels, rt_accum_select, rt_accum_add_pixels: no counterpart either (rendering to a per-pixel error
  *                          target with sparse pixel-list passes)
+ *   rt_render_pixels_path, rt_render_pixels_with: no counterpart either (which kernel family runs a pixel list of
+ *                          a mesh scene: the pool kernel of its full frame, or the fused per-lane walk)
  *   rt_scene_view, rt_accum_reproject: no counterpart either (camera views of one scene, and an accumulator's
  *                          history carried across a camera move)
  *   rt_accum_holes, rt_accum_fill: no counterpart either (after a reprojection, samples only for the pixels that
@@ -52,7 +54,8 @@ extern "C" {
                              the error-target calls (rt_render_pixels*, rt_accum_add_pixels, rt_accum_add_sub_pixels*,
                              rt_accum_counts, rt_accum_select*) and the views and reprojection (rt_scene_view,
                              rt_scene_get_view, rt_accum_reproject) and the hole fill (rt_accum_holes*,
-                             rt_accum_fill) */
+                             rt_accum_fill) and the pixel-list kernel families (rt_render_pixels_path,
+                             rt_render_pixels_with*, RT_LIST_*) */
 
 /* return codes */
 #define RT_OK 0
@@ -289,7 +292,9 @@ int rt_denoise_var_device(int32_t device, int32_t width, int32_t height, const d
  * (row 0 = top), strictly ascending, each < width * height. params must be the whole frame, as rt_accum_add requires
  * it: x0 = y0 = 0, tile_w = width, tile_h = height, row_step 0 or 1. Entry e of the outputs is pixel pixels[e]:
  * sub_out[e] (12 f64) is rt_render's sub_out of that pixel for the same seed, spp and flags, bit for bit, and
- * rgb_out[e] its RGB8, byte for byte. The f64 fused megakernel's per-vertex code runs it (k_render_list_f64):
+ * rgb_out[e] its RGB8, byte for byte. The f64 fused megakernel's per-vertex code runs it (k_render_list_f64), or, for
+ * a mesh scene whose full frame runs a pool kernel, that kernel's pixel-list instance (rt_render_pixels_path names the
+ * family; the bits are the same whichever runs):
  * RT_FLAG_MIS passes through, RT_FLAG_MEGAKERNEL is implied; RT_FLAG_FP32 and RT_FLAG_MESH_NEAREST are out of scope
  * (RT_E_INVAL). n_pixels * 4 must fit an int32. The host form checks the list (RT_E_INVAL before any device call);
  * n_pixels = 0 returns RT_OK without a launch and leaves the outputs untouched. cancel and stats as in rt_render;
@@ -302,6 +307,25 @@ int rt_render_pixels(const rt_scene* scene, const rt_render_params* params, cons
  * in-range list is the caller's contract here: it is not checked. */
 int rt_render_pixels_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
                             int64_t n_pixels, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats);
+
+/* The kernel family of a pixel-list render. */
+#define RT_LIST_AUTO  0
+#define RT_LIST_FUSED 1   /* k_render_list_f64 */
+#define RT_LIST_FPOOL 2   /* the flat-octree query pool */
+#define RT_LIST_ROLES 3   /* the role-split pool */
+/* path_out[0]: the kernel family rt_render_pixels takes for this scene, these params and a list of n_pixels;
+ * path_out[1]: the pool family this scene and these flags have at all (RT_LIST_FUSED: none). params and n_pixels
+ * are checked as rt_render_pixels checks them. No GPU needed. */
+int rt_render_pixels_path(const rt_scene* scene, const rt_render_params* params, int64_t n_pixels, int32_t path_out[2]);
+/* rt_render_pixels with the family chosen by the caller: RT_LIST_AUTO is rt_render_pixels; a family the scene has
+ * no instance of is RT_E_INVAL before any device call. Same bits whichever family runs. */
+int rt_render_pixels_with(const rt_scene* scene, const rt_render_params* params, const uint32_t* pixels,
+                          int64_t n_pixels, int32_t path, uint8_t* rgb_out, double* sub_out,
+                          const volatile int32_t* cancel, rt_render_stats* stats);
+/* rt_render_pixels_device with the family chosen by the caller, by the same rules. */
+int rt_render_pixels_with_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
+                                 int64_t n_pixels, int32_t path, void* d_rgb, void* d_sub, void* stream,
+                                 rt_render_stats* stats);
 
 /* Sparse passes into an accumulator. The first sparse merge gives the accumulator per-pixel counts (K_p, N_p), 8 bytes
  * per pixel (allocated together with a pixel-list buffer and the selection's scratch, about 12.2 bytes per pixel in

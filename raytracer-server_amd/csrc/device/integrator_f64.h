@@ -71,6 +71,27 @@ RT_DEV SubPixel subpixel_of(const RenderArgs& a, long p) {
     s.sy = s.sub >> 1;
     return s;
 }
+// Pixel-list renders: the SubPixel of unit u = 4 e + j of list entry e, with the frame pixel
+// p = pixels[e] = row * width + col (pid = p: the RNG key is the frame's, whatever the list).
+RT_DEV SubPixel subpixel_of_pixel(const RenderArgs& a, uint32_t p, int u) {
+    const uint32_t w = (uint32_t)a.width;
+    const uint32_t row = p / w;
+    SubPixel s;
+    s.sub = u & 3;
+    s.col = (int)(p - row * w);
+    s.yref = a.height - (int)row - 1;
+    s.pid = p;
+    s.sx = s.sub & 1;
+    s.sy = s.sub >> 1;
+    return s;
+}
+// The one place a pool kernel's unit id becomes a pixel: the frame instances (L = false) map the tile-local id,
+// the list instances (L = true) read the list (id < 4 n_pixels for every unit a ticket hands out).
+template <bool L>
+RT_DEV SubPixel unit_subpixel(const RenderArgs& a, const uint32_t* pixels, int id) {
+    if constexpr (L) return subpixel_of_pixel(a, pixels[id >> 2], id);
+    else return subpixel_of(a, id);
+}
 
 // Camera ray of sample `smp` of subpixel `sp` (server.rs:338-357): its direction and the sample's
 // RNG stream after the two camera draws.

@@ -547,9 +547,13 @@ __global__ __launch_bounds__(kBlk, W) void k_megakernel_flat_f64(DevScene sc_g, 
 #define RT_FPOOL_SINK 1  // A/B: shade_vertex writes the shadow query's ray into the LDS columns (LdsQuerySink)
 #endif
 
-template <int F, int W, int B = kBlk>
-__global__ __launch_bounds__(B, W) void k_megakernel_fpool_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
-                                                                 uint32_t* next_sub, long nsub, int pool_min, int refill) {
+// The kernel's body, shared by its frame instances (L = false: k_megakernel_fpool_f64, units are the tile's
+// subpixels) and its pixel-list instances (L = true: k_megakernel_fpool_list_f64, unit 4 e + j is subpixel j of the
+// frame pixel pixels[e]). Everything but unit_subpixel works on the compact unit id.
+template <int F, int B, bool L>
+__device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
+                                           uint32_t* next_sub, long nsub, int pool_min, int refill,
+                                           const uint32_t* __restrict__ pixels) {
     using C = Cfg<F | kCfgLdsObj>;  // the object table in LDS (path_f64.h rt_lds_objects)
     static_assert(C::mesh && C::compact && !C::bvh, "flat-mesh kernel: compact scenes, octree meshes");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves (path_f64.h: the diagnostic builds' per-wave LDS)");
@@ -805,7 +809,7 @@ __global__ __launch_bounds__(B, W) void k_megakernel_fpool_f64(DevScene sc_g, Re
             const bool need = active && !fresh && !nvalid && unit_has_next(a, id, s);
             if (refill > 0 && __popcll(__ballot(need)) >= refill) {
                 if (need) {
-                    const CameraSample nb = camera_sample(sc, a, subpixel_of(a, id), s + 1);
+                    const CameraSample nb = camera_sample(sc, a, unit_subpixel<L>(a, pixels, id), s + 1);
                     nbd[0] = nb.d.x; nbd[B] = nb.d.y; nbd[2 * B] = nb.d.z;
                     nbr[0] = nb.r0; nbr[B] = nb.r1;
                     nvalid = true;
@@ -818,7 +822,7 @@ __global__ __launch_bounds__(B, W) void k_megakernel_fpool_f64(DevScene sc_g, Re
         if (tr) {
             if (fresh) {
                 if (C::nospec && nvalid) begin_path(sc, CameraSample{v3(nbd[0], nbd[B], nbd[2 * B]), nbr[0], nbr[B]}, ps);
-                else begin_sample(sc, a, subpixel_of(a, id), s, ps);
+                else begin_sample(sc, a, unit_subpixel<L>(a, pixels, id), s, ps);
                 nvalid = false;
                 fresh = false;
             }
@@ -853,6 +857,20 @@ __global__ __launch_bounds__(B, W) void k_megakernel_fpool_f64(DevScene sc_g, Re
     }
     flush_count(a.counters, nverts);
     RT_DBG_TFLUSH();
+}
+
+template <int F, int W, int B = kBlk>
+__global__ __launch_bounds__(B, W) void k_megakernel_fpool_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
+                                                                 uint32_t* next_sub, long nsub, int pool_min, int refill) {
+    fpool_body<F, B, false>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, nullptr);
+}
+// The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
+template <int F, int W, int B = kBlk>
+__global__ __launch_bounds__(B, W) void k_megakernel_fpool_list_f64(DevScene sc_g, RenderArgs a_g,
+                                                                      double* __restrict__ sub_buf, uint32_t* next_sub,
+                                                                      long nsub, int pool_min, int refill,
+                                                                      const uint32_t* __restrict__ pixels) {
+    fpool_body<F, B, true>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, pixels);
 }
 
 template <int F, int W, int B = kBlk>
@@ -921,6 +939,45 @@ hipError_t launch_megakernel_flat_f64(const DevScene& sc, const RenderArgs& a_in
         }
     }
 #undef RT_FLAT_CASE
+    launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
+    return hipGetLastError();
+}
+
+template <int F, int W, int B = kBlk>
+static void launch_fpool_list(const DevScene& sc, RenderArgs& a, const uint32_t* pixels, double* sub_buf,
+                              uint32_t* next_sub, long nsub, double* tail_buf, size_t tail_cap, int pool_min, int refill,
+                              hipStream_t st) {
+    const long blocks = resident_blocks(k_megakernel_fpool_list_f64<F, W, B>, (nsub + B - 1) / B, B);
+    plan_tail(a, nsub, blocks * B, tail_buf, tail_cap, tail_split_x2(nsub, blocks * B));
+    hipLaunchKernelGGL((k_megakernel_fpool_list_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
+                       next_sub, nsub, pool_min, refill, pixels);
+}
+
+// The query pool over a pixel list (kernels.h list_pool_family == kListFpool: flat octrees, no Phong
+// object): launch_megakernel_flat_f64's product instances and planning with nsub = 4 n_pixels compact units, the
+// split tail included. Called by launch_render_list_f64 after the ticket counter is reset.
+hipError_t launch_render_list_flat_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* pixels, long n_pixels,
+                                       double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
+                                       hipStream_t st) {
+    const long nsub = n_pixels * 4;
+    RenderArgs a = a_in;
+    static const int pool_min = env_int("RT_MK_FPOOL_MIN", 56);       // as launch_megakernel_flat_f64
+    static const int nospec = env_int("RT_MK_NOSPEC", 1);
+    static const int fpool_refill = env_int("RT_MK_FPOOL_REFILL", 20);
+    if (a.features & 2) return hipErrorInvalidValue;  // Phong scenes stay on k_render_list_f64
+    if (nospec && (a.features & 32)) {  // no mirror object: the 1024-thread block shape
+        switch (a.features & 15) {
+            case 9: launch_fpool_list<9 | 32, RT_FPOOL_BLOCK / 256, RT_FPOOL_BLOCK>(sc, a, pixels, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
+            case 13: launch_fpool_list<13 | 32, RT_FPOOL_BLOCK / 256, RT_FPOOL_BLOCK>(sc, a, pixels, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (a.features & 15) {
+            case 9: launch_fpool_list<9, 3>(sc, a, pixels, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
+            case 13: launch_fpool_list<13, 3>(sc, a, pixels, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
+            default: return hipErrorInvalidValue;
+        }
+    }
     launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
     return hipGetLastError();
 }

@@ -1,4 +1,8 @@
 // Pixel-list render for gfx950: k_render_list_f64 traces only the listed frame pixels.
+// launch_render_list_f64 runs it for analytic scenes, and for mesh scenes whose frame kernel has no list instance
+// (Phong mesh scenes, octrees without slot tables) or whose list is short; the other mesh scenes' lists go through
+// the list instances of the frame's own pool kernels (k_megakernel_fpool_list_f64, k_megakernel_roles_list_f64:
+// DESIGN.md §16), which give the same bits.
 //
 // The sparse passes of a render to a per-pixel error target (rt_accum_select's active pixels) have no rectangular
 // tile for the megakernels' ticket -> tile-local subpixel map (integrator_f64.h subpixel_of), so this kernel builds
@@ -30,20 +34,6 @@ typedef __attribute__((address_space(3))) uint64_t LdsU64;
 #ifndef RT_MK_MIN_RUN
 #define RT_MK_MIN_RUN 32  // as render_f64.hip
 #endif
-
-// The SubPixel of unit u = 4 e + j with p = pixels[e].
-RT_DEV SubPixel subpixel_of_pixel(const RenderArgs& a, uint32_t p, int u) {
-    const uint32_t w = (uint32_t)a.width;
-    const uint32_t row = p / w;
-    SubPixel s;
-    s.sub = u & 3;
-    s.col = (int)(p - row * w);
-    s.yref = a.height - (int)row - 1;
-    s.pid = p;
-    s.sx = s.sub & 1;
-    s.sy = s.sub >> 1;
-    return s;
-}
 
 // a.n_whole = 4 n_pixels units in runs of a.unit_subs per ticket (a.n_wunits tickets); a.chunk_lg = 0, a.tail_cps = 1.
 template <int F, int W>
@@ -172,16 +162,26 @@ static void launch_list_shape(const DevScene& sc, const RenderArgs& a, const uin
 }
 
 hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* pixels, long n_pixels,
-                                  double* sub_buf, uint32_t* next_unit, hipStream_t st) {
+                                  double* sub_buf, uint32_t* next_unit, int family, double* tail_buf, size_t tail_cap,
+                                  hipStream_t st) {
     if (n_pixels <= 0 || a_in.n_samples <= 0) return hipSuccess;
     if (n_pixels > 0x7fffffffL / 4) return hipErrorInvalidValue;
     RenderArgs a = a_in;
-    a.n_whole = (int32_t)(n_pixels * 4);  // every unit is a whole subpixel: no split tail
+    a.n_whole = (int32_t)(n_pixels * 4);  // every unit is a whole subpixel unless a pool launcher plans a split tail
     a.chunk_lg = 0;
     a.tail_cps = 1;
     a.tail_buf = nullptr;
+    t_tail_plan = TailPlan{};
     hipError_t e = hipMemsetAsync(next_unit, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
+    // a mesh scene's pool family (the kernel its full frame runs); a family the scene has no
+    // instance of is an error, never a quiet change of kernel
+    if (family != kListFused) {
+        if (family != list_pool_family(a, sc.node_slot != nullptr)) return hipErrorInvalidValue;
+        if (family == kListFpool)
+            return launch_render_list_flat_f64(sc, a, pixels, n_pixels, sub_buf, next_unit, tail_buf, tail_cap, st);
+        return launch_render_list_roles_f64(sc, a, pixels, n_pixels, sub_buf, next_unit, tail_buf, tail_cap, st);
+    }
     static const int refill = env_int("RT_MK_CAM_REFILL", 40);  // the megakernel's camera-ring refill threshold
 #define RT_LIST_CASE(F)                                                       \
     case F:                                                                   \

@@ -949,9 +949,12 @@ RT_DEV void role_query_closest(const RP& P, int p, const HitRec& h, uint32_t nea
     P.I(RI_NEAR, p) = (int32_t)near;
 }
 
-template <int F, int W, bool S, int B = RoleShape<Cfg<F>>::block>
-__global__ __launch_bounds__(B, W) void k_megakernel_roles_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
-                                                                uint32_t* next_sub, long nsub) {
+// The kernel's body, shared by its frame instances (L = false: k_megakernel_roles_f64, units are the tile's
+// subpixels) and its pixel-list instances (L = true: k_megakernel_roles_list_f64, unit 4 e + j is subpixel j of the
+// frame pixel pixels[e]). Everything but unit_subpixel works on the compact unit id.
+template <int F, bool S, int B, bool L>
+__device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
+                                           uint32_t* next_sub, long nsub, const uint32_t* __restrict__ pixels) {
     using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0)>;
     static_assert(C::mesh && C::compact && !C::bvh, "the role-split pool walks octrees");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves, at most 16 (path_f64.h: the diagnostic builds' per-wave LDS)");
@@ -1207,7 +1210,7 @@ __global__ __launch_bounds__(B, W) void k_megakernel_roles_f64(DevScene sc_g, Re
             if (retire) p = -1;
             // the next ray: the path going on, or its unit's next sample
             if (p >= 0 && !park && (rs == RS_TRACE || rs == RS_FRESH)) {
-                if (rs == RS_FRESH) begin_sample(sc, a, subpixel_of(a, id), s, ps);
+                if (rs == RS_FRESH) begin_sample(sc, a, unit_subpixel<L>(a, pixels, id), s, ps);
                 RT_DBG_TSTART(t_ta);
                 const RayInv wi = make_inv(ps.ray.d);
                 const HitRec h = trace_analytic<C>(sc, ps.ray, wi);
@@ -1231,6 +1234,19 @@ __global__ __launch_bounds__(B, W) void k_megakernel_roles_f64(DevScene sc_g, Re
     }
     flush_count(a.counters, nverts);
     RT_DBG_TFLUSH();
+}
+
+template <int F, int W, bool S, int B = RoleShape<Cfg<F>>::block>
+__global__ __launch_bounds__(B, W) void k_megakernel_roles_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
+                                                                uint32_t* next_sub, long nsub) {
+    roles_body<F, S, B, false>(sc_g, a_g, sub_buf, next_sub, nsub, nullptr);
+}
+// The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
+template <int F, int W, bool S, int B = RoleShape<Cfg<F>>::block>
+__global__ __launch_bounds__(B, W) void k_megakernel_roles_list_f64(DevScene sc_g, RenderArgs a_g,
+                                                                     double* __restrict__ sub_buf, uint32_t* next_sub,
+                                                                     long nsub, const uint32_t* __restrict__ pixels) {
+    roles_body<F, S, B, true>(sc_g, a_g, sub_buf, next_sub, nsub, pixels);
 }
 
 template <int F, bool S = (RT_WALK_TIGHT != 0)>
@@ -1302,6 +1318,33 @@ hipError_t launch_megakernel_mesh_f64(const DevScene& sc, const RenderArgs& a, d
 #undef RT_MMB_CASE
 #undef RT_MM_CASE
 #undef RT_MM_AB
+    return hipGetLastError();
+}
+
+template <int F, bool S = (RT_WALK_TIGHT != 0)>
+static void launch_roles_list(const DevScene& sc, const RenderArgs& a_in, const uint32_t* pixels, double* sub_buf,
+                              uint32_t* next_sub, long nsub, double* tail_buf, size_t tail_cap, hipStream_t st) {
+    constexpr int B = RoleShape<Cfg<F>>::block, W = B / 256;
+    const long blocks = resident_blocks(k_megakernel_roles_list_f64<F, W, S>, (nsub + B - 1) / B, B);
+    RenderArgs a = a_in;
+    plan_tail(a, nsub, blocks * RoleLayout<Cfg<F>>::paths, tail_buf, tail_cap, 12, 1, 64);  // as launch_roles
+    hipLaunchKernelGGL((k_megakernel_roles_list_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
+                       next_sub, nsub, pixels);
+    launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
+}
+
+// The role-split pool over a pixel list (kernels.h list_pool_family == kListRoles: compact scenes
+// with slot tables and an octree of >= 64 nodes, no Phong object): launch_roles' planning with nsub = 4 n_pixels
+// compact units, the split tail included. Called by launch_render_list_f64 after the ticket counter is reset.
+hipError_t launch_render_list_roles_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
+                                        double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
+                                        hipStream_t st) {
+    if (!sc.node_slot) return hipErrorInvalidValue;  // octrees without slot tables stay on k_render_list_f64
+    switch (a.features & 31) {
+        case 9: launch_roles_list<9>(sc, a, pixels, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, st); break;
+        case 13: launch_roles_list<13>(sc, a, pixels, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, st); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

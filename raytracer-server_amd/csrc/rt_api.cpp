@@ -1130,7 +1130,12 @@ struct RenderCall {
 
 // The kernels' view of `p` on the uploaded scene `ds`: frame, tile, samples, seed, camera frame and the Cfg<F>
 // feature bits (no output pointers, no scheduling).
+rt::RenderArgs make_render_args(const rt_scene* s, const rt_render_params* p, int32_t compact);
 rt::RenderArgs make_render_args(const rt_scene* s, const rt_render_params* p, const rt::DevScene& ds) {
+    return make_render_args(s, p, ds.compact);
+}
+// The same from the host side alone (compact: fill_compact's answer, which is what upload gives DevScene::compact).
+rt::RenderArgs make_render_args(const rt_scene* s, const rt_render_params* p, int32_t compact) {
     rt::RenderArgs a{};
     a.width = p->width;
     a.height = p->height;
@@ -1147,7 +1152,7 @@ rt::RenderArgs make_render_args(const rt_scene* s, const rt_render_params* p, co
             phong |= o.brdf == RT_BRDF_PHONG;
             spec |= o.brdf == RT_BRDF_SPECULAR;
         }
-        a.features = (s->host.meshes.empty() ? 0 : 1) | (phong ? 2 : 0) | (a.mis ? 4 : 0) | (ds.compact ? 8 : 0) |
+        a.features = (s->host.meshes.empty() ? 0 : 1) | (phong ? 2 : 0) | (a.mis ? 4 : 0) | (compact ? 8 : 0) |
                      (spec ? 0 : 32);
         if ((p->flags & RT_FLAG_MESH_NEAREST) && !s->host.meshes.empty()) a.features |= 16;
         for (const auto& m : s->host.meshes) a.mesh_nodes = std::max(a.mesh_nodes, (int32_t)m.octree.size());
@@ -1167,6 +1172,30 @@ hipError_t finalize_rgb(int32_t width, int32_t height, const double* d_sub, uint
     a.th = height;
     a.rgb_out = d_rgb;
     return rt::launch_finalize_f64(a, d_sub, st);
+}
+
+// Split-tail scratch for an f64 megakernel launch over npix pixels (a frame's tile, or a pixel list through a pool
+// kernel) on the current device (megakernel_common.h plan_tail): the samples after chunk 0 of the subpixels a
+// launch splits — kernels.h tail_split_x2 / 2 per resident lane in the analytic and flat-mesh kernels
+// (no more than 1024 lanes per CU: 4 waves/SIMD, the 1024-thread query pool), so 1536 per CU (393,216 on
+// 256 CUs: 2.1 GB at 1024 spp), 2048 for frames of <= 4 subpixels per lane; six per path slot in the
+// mesh walk kernels (<= 1024 slots per CU) — at most 3 GB. A smaller buffer only splits fewer
+// subpixels (plan_tail; rt_debug_last_split reports the split wanted and made), with the same frame bits.
+void ensure_tail_scratch(rt::Workspace* ws, const rt::RenderArgs& a, size_t npix) {
+    const bool walk = (a.features & 1) && !a.all_flat;
+    int dev = 0, ncu = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const size_t per_sub = rt::tail_scratch_per_subpixel(a.n_samples);
+    // (A/B builds: RT_MK_TAIL_SCRATCH_PER_CU / RT_MK_TAIL_SCRATCH_MB override both bounds, ab_knobs.h)
+    const long ncu_lanes = (long)std::max(ncu, 1) * 1024;
+    const size_t per_cu = (size_t)rt::ab_knob("RT_MK_TAIL_SCRATCH_PER_CU",
+                                              walk ? 6 * 1024 : 512 * rt::tail_split_x2((long)npix * 4, ncu_lanes));
+    const size_t cap = (size_t)rt::ab_knob("RT_MK_TAIL_SCRATCH_MB", 3072) << 20;
+    const size_t want = std::min<size_t>(cap, per_sub * std::min<size_t>(npix * 4, (size_t)std::max(ncu, 1) * per_cu));
+    if (per_sub > 0 && want >= per_sub) {
+        if (ws->ensure_tail(want) != hipSuccess) (void)hipGetLastError();  // no tail split then
+    }
 }
 
 // Enqueue one render on `st` (device buffers); returns without waiting for the device (except in
@@ -1220,26 +1249,7 @@ int render_enqueue(rt_scene* s, const rt_render_params* p, uint8_t* d_rgb, doubl
         if (e == hipSuccess && a.n_samples <= 0) e = hipMemsetAsync(sub, 0, npix * 12 * sizeof(double), st);
         if (e == hipSuccess) {
             a.counters = ps ? ws->counters : nullptr;
-            // split-tail scratch (megakernel_common.h plan_tail): the samples after chunk 0 of the subpixels a
-            // launch splits — kernels.h tail_split_x2 / 2 per resident lane in the analytic and flat-mesh kernels
-            // (no more than 1024 lanes per CU: 4 waves/SIMD, the 1024-thread query pool), so 1536 per CU (393,216 on
-            // 256 CUs: 2.1 GB at 1024 spp), 2048 for frames of <= 4 subpixels per lane; six per path slot in the
-            // mesh walk kernels (<= 1024 slots per CU) — at most 3 GB. A smaller buffer only splits fewer
-            // subpixels (plan_tail; rt_debug_last_split reports the split wanted and made), with the same frame bits.
-            const bool walk = (a.features & 1) && !a.all_flat;
-            int dev = 0, ncu = 256;
-            (void)hipGetDevice(&dev);
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-            const size_t per_sub = rt::tail_scratch_per_subpixel(a.n_samples);
-            // (A/B builds: RT_MK_TAIL_SCRATCH_PER_CU / RT_MK_TAIL_SCRATCH_MB override both bounds, ab_knobs.h)
-            const long ncu_lanes = (long)std::max(ncu, 1) * 1024;
-            const size_t per_cu = (size_t)rt::ab_knob("RT_MK_TAIL_SCRATCH_PER_CU",
-                                                      walk ? 6 * 1024 : 512 * rt::tail_split_x2((long)npix * 4, ncu_lanes));
-            const size_t cap = (size_t)rt::ab_knob("RT_MK_TAIL_SCRATCH_MB", 3072) << 20;
-            const size_t want = std::min<size_t>(cap, per_sub * std::min<size_t>(npix * 4, (size_t)std::max(ncu, 1) * per_cu));
-            if (!fp32 && per_sub > 0 && want >= per_sub) {
-                if (ws->ensure_tail(want) != hipSuccess) (void)hipGetLastError();  // no tail split then
-            }
+            if (!fp32) ensure_tail_scratch(ws.get(), a, npix);
             if (fp32) {
                 static const int brute = (int)rt::ab_knob("RT_F32_BRUTE", 16);
                 a.f32_brute = brute;
@@ -2114,13 +2124,47 @@ int check_pixel_list(const char* who, const uint32_t* pixels, int64_t n_pixels, 
     return RT_OK;
 }
 
-// render_enqueue for a pixel list (k_render_list_f64 + k_finalize_f64 on the compact buffer); arguments checked by
-// check_render_pixels, n_pixels > 0. d_rgb and d_sub may be null.
+// The kernel family of a pixel-list render. The pool family a scene has under its flags is the one its
+// full frame runs (kernels.h list_pool_family), decided from the host-side packed scene as check_diag decides its
+// forms; `path` asks for a family or leaves the choice to the length rule.
+static_assert(RT_LIST_FUSED == rt::kListFused && RT_LIST_FPOOL == rt::kListFpool && RT_LIST_ROLES == rt::kListRoles,
+              "kernels.h mirrors rt_ffi.h's family ids");
+int list_pool_of(const rt_scene* s, const rt_render_params* p) {
+    int32_t compact = 0;
+    {
+        rt::CompactTab tab;
+        fill_compact(s->packed, &tab, &compact);
+    }
+    return rt::list_pool_family(make_render_args(s, p, compact), !s->packed.slots.empty());
+}
+// The automatic choice: the scene's pool at every list length. On the cubes and the unicorn the pool kernels were never
+// slower than k_render_list_f64 for lists from every pixel of a 1920x1080 frame down to one pixel (DESIGN.md §16's
+// table), so no length threshold exists; scene, flags and length decide alone, so the answer needs no device.
+int list_auto_family(int pool, int64_t /*n_pixels*/) { return pool; }
+// path (a caller's choice, or RT_LIST_AUTO) -> the family that runs, or RT_E_INVAL for an unknown path or a family the
+// scene has no instance of.
+int list_family_of(const char* who, const rt_scene* s, const rt_render_params* p, int64_t n_pixels, int32_t path,
+                   int* family) {
+    if (path < RT_LIST_AUTO || path > RT_LIST_ROLES) return fail(RT_E_INVAL, std::string(who) + ": unknown kernel family");
+    const int pool = list_pool_of(s, p);
+    if (path == RT_LIST_AUTO) *family = list_auto_family(pool, n_pixels);
+    else if (path == RT_LIST_FUSED || path == pool) *family = path;
+    else return fail(RT_E_INVAL, std::string(who) + ": the scene has no pixel-list instance of this kernel family");
+    return RT_OK;
+}
+
+// render_enqueue for a pixel list (the list kernel of `path`'s family + k_finalize_f64 on the compact buffer);
+// arguments checked by check_render_pixels (and list_family_of for a path other than RT_LIST_AUTO), n_pixels > 0.
+// d_rgb and d_sub may be null.
 int render_pixels_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t* d_pixels, int64_t n_pixels,
-                          uint8_t* d_rgb, double* d_sub, hipStream_t st, const int32_t* dcancel, PendingStats* ps) {
+                          uint8_t* d_rgb, double* d_sub, hipStream_t st, const int32_t* dcancel, PendingStats* ps,
+                          int32_t path = RT_LIST_AUTO) {
+    int family = RT_LIST_FUSED;
+    int rc = list_family_of("pixel-list render", s, p, n_pixels, path, &family);
+    if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     rt::DevScene ds;
-    const int rc = upload(s, p->device, &ds);
+    rc = upload(s, p->device, &ds);
     if (rc != RT_OK) return rc;
     rt::RenderArgs a = make_render_args(s, p, ds);
     a.x0 = 0;
@@ -2150,7 +2194,10 @@ int render_pixels_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t
     if (e == hipSuccess && a.n_samples <= 0) e = hipMemsetAsync(sub, 0, (size_t)n_pixels * 12 * sizeof(double), st);
     if (e == hipSuccess) {
         a.counters = ps ? ws->counters : nullptr;
-        e = rt::launch_render_list_f64(ds, a, d_pixels, (long)n_pixels, sub, (uint32_t*)(ws->counters + 4), st);
+        // the pool kernels split their last units into chunks of samples: the frame's scratch rule, for this many pixels
+        if (family != RT_LIST_FUSED) ensure_tail_scratch(ws.get(), a, (size_t)n_pixels);
+        e = rt::launch_render_list_f64(ds, a, d_pixels, (long)n_pixels, sub, (uint32_t*)(ws->counters + 4), family,
+                                       ws->tail_buf, ws->tail_cap, st);
     }
     if (e == hipSuccess && d_rgb) e = rt::launch_finalize_f64(a, sub, st);
     if (e == hipSuccess && ps) e = hipEventRecord(ps->e1, st);
@@ -2241,9 +2288,12 @@ int select_run(rt_accum* a, float abs_tol, float rel_tol, int32_t max_n, uint32_
 
 }  // namespace
 
-int rt_render_pixels_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
-                            int64_t n_pixels, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats) {
+int rt_render_pixels_with_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
+                                 int64_t n_pixels, int32_t path, void* d_rgb, void* d_sub, void* stream,
+                                 rt_render_stats* stats) {
     int rc = check_render_pixels("rt_render_pixels_device", scene, params, d_pixels, n_pixels);
+    int family;
+    if (rc == RT_OK) rc = list_family_of("rt_render_pixels_device", scene, params, n_pixels, path, &family);
     if (rc != RT_OK) return rc;
     if (n_pixels == 0) {
         if (stats) std::memset(stats, 0, sizeof *stats);
@@ -2255,14 +2305,22 @@ int rt_render_pixels_device(const rt_scene* scene, const rt_render_params* param
     PendingStats ps;
     ps.out = stats;
     rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), params, (const uint32_t*)d_pixels, n_pixels, (uint8_t*)d_rgb,
-                               (double*)d_sub, st, nullptr, stats ? &ps : nullptr);
+                               (double*)d_sub, st, nullptr, stats ? &ps : nullptr, path);
     return stats_sync(rc, st, stats ? &ps : nullptr);
 }
 
-int rt_render_pixels(const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels, int64_t n_pixels,
-                     uint8_t* rgb_out, double* sub_out, const volatile int32_t* cancel, rt_render_stats* stats) {
+int rt_render_pixels_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
+                            int64_t n_pixels, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats) {
+    return rt_render_pixels_with_device(scene, params, d_pixels, n_pixels, RT_LIST_AUTO, d_rgb, d_sub, stream, stats);
+}
+
+int rt_render_pixels_with(const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels, int64_t n_pixels,
+                          int32_t path, uint8_t* rgb_out, double* sub_out, const volatile int32_t* cancel,
+                          rt_render_stats* stats) {
     int rc = check_render_pixels("rt_render_pixels", scene, p, pixels, n_pixels);
     if (rc == RT_OK) rc = check_pixel_list("rt_render_pixels", pixels, n_pixels, (int64_t)p->width * p->height);
+    int family;
+    if (rc == RT_OK) rc = list_family_of("rt_render_pixels", scene, p, n_pixels, path, &family);
     if (rc != RT_OK) return rc;
     if (n_pixels == 0) {
         if (stats) std::memset(stats, 0, sizeof *stats);
@@ -2282,8 +2340,23 @@ int rt_render_pixels(const rt_scene* scene, const rt_render_params* p, const uin
     const hipError_t e = hipMemcpyAsync(d_pix, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, call.cs.st);
     if (e != hipSuccess) return oom_or_hip(e, "rt_render_pixels");
     rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), p, d_pix, n_pixels, rgb_out ? d_rgb : nullptr, d_sub,
-                               call.cs.st, call.mirror.dev, &call.ps);
+                               call.cs.st, call.mirror.dev, &call.ps, path);
     return call.finish("rt_render_pixels", rc, {{rgb_out, d_rgb, n * 3}, {sub_out, d_sub, b_sub}});
+}
+
+int rt_render_pixels(const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels, int64_t n_pixels,
+                     uint8_t* rgb_out, double* sub_out, const volatile int32_t* cancel, rt_render_stats* stats) {
+    return rt_render_pixels_with(scene, p, pixels, n_pixels, RT_LIST_AUTO, rgb_out, sub_out, cancel, stats);
+}
+
+int rt_render_pixels_path(const rt_scene* scene, const rt_render_params* p, int64_t n_pixels, int32_t path_out[2]) {
+    if (!path_out) return fail(RT_E_INVAL, "rt_render_pixels_path: null argument");
+    // (the list itself plays no part: a non-null stand-in passes check_render_pixels' null-list rule)
+    const int rc = check_render_pixels("rt_render_pixels_path", scene, p, path_out, n_pixels);
+    if (rc != RT_OK) return rc;
+    path_out[1] = list_pool_of(scene, p);
+    path_out[0] = list_auto_family(path_out[1], n_pixels);
+    return RT_OK;
 }
 
 int rt_accum_add_pixels(void* accum, const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels,

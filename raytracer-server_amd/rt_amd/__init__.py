@@ -9,7 +9,8 @@ Reference interface it mirrors (SuneelFreimuth/raytracer-server):
 Beyond the reference: render_features / denoise / render_denoised, denoised previews at low spp
 (rt_render_features, rt_denoise). Accumulator / denoise_var / render_progressive: progressive refinement
 (rt_accum_*, rt_denoise_var). render_pixels / Accumulator.select / add_pixels / render_to_error: rendering
-to a per-pixel error target with sparse pixel-list passes (rt_render_pixels, rt_accum_select).
+to a per-pixel error target with sparse pixel-list passes (rt_render_pixels, rt_accum_select; DESIGN.md §13);
+render_pixels(path=...) / render_pixels_path: the kernel family that runs a mesh scene's list.
 Scene.view / Scene.camera / look_at / Accumulator.reproject_from / render_interactive: camera views of one scene and
 an accumulator's history carried across a camera move (rt_scene_view, rt_accum_reproject).
 Accumulator.holes / Accumulator.fill / render_interactive(fill_spp, refresh) / FILL_DEFAULTS: after a reprojection,
@@ -35,6 +36,9 @@ FLAG_FP32 = 1 << 2
 FLAG_MESH_NEAREST = 1 << 3  # Mesh::intersect without the octree (geometry.rs:886-903), BVH on the device
 # query forms of Scene.diag_trace / diag_visible (include/rt_diag.h RT_DIAG_*)
 DIAG_FUSED, DIAG_FUSED_G0, DIAG_SPLIT_SLOTS, DIAG_SPLIT_KIDS, DIAG_SPLIT_FLAT, DIAG_FUSED_G1 = range(6)
+# kernel families of a pixel-list render (include/rt_ffi.h RT_LIST_*): the automatic choice, k_render_list_f64, the
+# flat-octree query pool, the role-split pool
+LIST_AUTO, LIST_FUSED, LIST_FPOOL, LIST_ROLES = range(4)
 
 BRDF_DIFFUSE, BRDF_SPECULAR, BRDF_PHONG = 0, 1, 2
 GEOM_SPHERE, GEOM_PLANE, GEOM_MESH = 0, 1, 2
@@ -92,7 +96,8 @@ _EXPORTS = ["rt_scene_load_toml", "rt_scene_create", "rt_scene_destroy", "rt_sce
             "rt_denoise_var_device", "rt_render_pixels", "rt_render_pixels_device", "rt_accum_add_pixels",
             "rt_accum_add_sub_pixels", "rt_accum_add_sub_pixels_device", "rt_accum_counts", "rt_accum_select",
             "rt_accum_select_device", "rt_scene_view", "rt_scene_get_view", "rt_accum_reproject", "rt_accum_holes",
-            "rt_accum_holes_device", "rt_accum_fill"]
+            "rt_accum_holes_device", "rt_accum_fill", "rt_render_pixels_path", "rt_render_pixels_with",
+            "rt_render_pixels_with_device"]
 
 
 def _load():
@@ -142,6 +147,9 @@ def _load():
     U32, I64, D = ctypes.c_uint32, ctypes.c_int64, ctypes.c_double
     L.rt_render_pixels.argtypes = [vp, P(RenderParams), P(U32), I64, P(ctypes.c_uint8), P(D), P(I), P(RenderStats)]
     L.rt_render_pixels_device.argtypes = [vp, P(RenderParams), vp, I64, vp, vp, vp, P(RenderStats)]
+    L.rt_render_pixels_path.argtypes = [vp, P(RenderParams), I64, P(I)]
+    L.rt_render_pixels_with.argtypes = [vp, P(RenderParams), P(U32), I64, I, P(ctypes.c_uint8), P(D), P(I), P(RenderStats)]
+    L.rt_render_pixels_with_device.argtypes = [vp, P(RenderParams), vp, I64, I, vp, vp, vp, P(RenderStats)]
     L.rt_accum_add_pixels.argtypes = [vp, vp, P(RenderParams), P(U32), I64, P(I), P(RenderStats)]
     L.rt_accum_add_sub_pixels.argtypes = [vp, P(U32), I64, P(D), I]
     L.rt_accum_add_sub_pixels_device.argtypes = [vp, vp, I64, vp, I, vp]
@@ -637,21 +645,32 @@ def look_at(pos, target, up=(0.0, 1.0, 0.0), fov=0.5135):
 
 
 def render_pixels(scene, width, height, pixels, spp, seed=0x5EED, mis=False, device=0, want_sub=False, want_rgb=True,
-                  cancel=None):
-    """Renders only the listed pixels of the width x height frame (rt_render_pixels): pixels are strictly ascending ids
-    row * width + col. Returns (rgb[n, 3] u8 or None, sub[n, 4, 3] f64 or None, stats); entry e is what render gives
-    for pixel pixels[e], bit for bit. f64 fused megakernel only."""
+                  cancel=None, path=LIST_AUTO):
+    """Renders only the listed pixels of the width x height frame (rt_render_pixels_with): pixels are strictly ascending
+    ids row * width + col. Returns (rgb[n, 3] u8 or None, sub[n, 4, 3] f64 or None, stats); entry e is what render gives
+    for pixel pixels[e], bit for bit. f64 megakernels only. path: LIST_AUTO (rt_render_pixels' own choice, see
+    render_pixels_path) or the kernel family to run; a family the scene has no instance of raises."""
     px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
     p = make_params(width, height, spp, seed, None, FLAG_MEGAKERNEL | (FLAG_MIS if mis else 0), device, 1)
     rgb = np.zeros((px.size, 3), dtype=np.uint8) if want_rgb else None
     sub = np.zeros((px.size, 4, 3), dtype=np.float64) if want_sub else None
     st = RenderStats()
-    rc = _check(lib.rt_render_pixels(scene.handle, ctypes.byref(p), _ptr(px, ctypes.c_uint32), px.size,
-                                     _ptr(rgb, ctypes.c_uint8), _ptr(sub, ctypes.c_double),
-                                     ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st)))
+    rc = _check(lib.rt_render_pixels_with(scene.handle, ctypes.byref(p), _ptr(px, ctypes.c_uint32), px.size, path,
+                                          _ptr(rgb, ctypes.c_uint8), _ptr(sub, ctypes.c_double),
+                                          ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st)))
     out = st.as_dict()
     out["cancelled"] = rc == RT_CANCELLED
     return rgb, sub, out
+
+
+def render_pixels_path(scene, width, height, spp, n_pixels, mis=False, flags=0):
+    """(family, pool) of a pixel-list render (rt_render_pixels_path): the LIST_* family render_pixels takes for a list
+    of n_pixels of this frame, and the pool family the scene has under these flags at all (LIST_FUSED: none). Needs no
+    GPU."""
+    p = make_params(width, height, spp, 0, None, FLAG_MEGAKERNEL | (FLAG_MIS if mis else 0) | flags, 0, 1)
+    out = (ctypes.c_int32 * 2)()
+    _check(lib.rt_render_pixels_path(scene.handle, ctypes.byref(p), n_pixels, out))
+    return int(out[0]), int(out[1])
 
 
 def denoise_var(sub, feat, var, levels=None, sigma_c=None, sigma_n=None, sigma_z=None, sigma_a=None,

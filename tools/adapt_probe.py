@@ -7,6 +7,11 @@
       active, each interleaved with rt_render_device of the full frame at 16 spp; then rt_accum_select_device and
       rt_accum_add_sub_pixels_device. Reports Msamples/s, the 100 % list's rate over the full-frame megakernel's, and the
       break-even fraction (the list size at which a sparse pass costs a full pass).
+  python tools/adapt_probe.py time --scene cubes|flying_unicorn [--family both|fused|pool|auto] [--log ...]
+      DESIGN.md §16, the same protocol for one scene and chosen kernel families (rt_render_pixels_with_device): lists of
+      every pixel and every 2nd, 10th, 100th and 1000th pixel (--strides) at 16 spp, each family's list render interleaved with
+      rt_render_device of the full frame; `both` runs k_render_list_f64 and the scene's pool side by side and reports the
+      shortest list from which the pool is never slower (the automatic choice's threshold).
   python tools/adapt_probe.py target [--size 96x72] [--log profiles/adapt_target.log]
       The three scenes with abs_tol in {0.03, 0.04, 0.06}: two full 8-spp passes, up to 30 sparse passes of 16 spp; mean
       and max spp, passes, and the linear RMSE against a 4096-spp frame of seed 999 over that of a uniform accumulation
@@ -76,9 +81,66 @@ def _c_of(sub):
     return px
 
 
+FAMILY_NAMES = {rt_amd.LIST_AUTO: "auto", rt_amd.LIST_FUSED: "fused", rt_amd.LIST_FPOOL: "fpool", rt_amd.LIST_ROLES: "roles"}
+
+
+def cmd_time_families(args):
+    """One scene, strided lists, the chosen kernel families against the full frame."""
+    log = Log(args.log)
+    w, h = _size(args.size)
+    npix, spp = w * h, 16
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+    st = V(stream) if stream else None
+    sc = _scene(args.scene)
+    p = rt_amd.make_params(w, h, spp, 0x5EED, None, rt_amd.FLAG_MEGAKERNEL, 0, 1)
+    pool = rt_amd.render_pixels_path(sc, w, h, spp, npix)[1]
+    fams = {"both": [rt_amd.LIST_FUSED, pool], "fused": [rt_amd.LIST_FUSED], "pool": [pool],
+            "auto": [rt_amd.LIST_AUTO]}[args.family]
+    fams = list(dict.fromkeys(fams))  # a scene without a pool: the fused kernel once
+    rgb = torch.zeros(npix * 3, dtype=torch.uint8, device=dev)
+    sub = torch.zeros(npix * 12, dtype=torch.float64, device=dev)
+    lsub = torch.zeros(npix * 12, dtype=torch.float64, device=dev)
+    ids_d = torch.zeros(npix, dtype=torch.int32, device=dev)
+
+    def full():
+        rt_amd.render_device(sc, p, rgb.data_ptr(), sub.data_ptr(), stream)
+
+    def listed(n, fam):
+        def fn():
+            rt_amd._check(rt_amd.lib.rt_render_pixels_with_device(sc.handle, ctypes.byref(p), V(ids_d.data_ptr()), n, fam,
+                                                                  None, V(lsub.data_ptr()), st, None))
+        return fn
+
+    log(f"# adapt_probe time: {args.scene} {w}x{h}, {spp} spp, median of {args.reps} after 3 warm-up calls (HIP events, "
+        f"one process, each list interleaved with the full frame); the scene's pool: {FAMILY_NAMES[pool]}")
+    log("every k-th  n_pixels  family   list ms   full ms  list Ms/s  full Ms/s  list/full time  auto takes")
+    times = {}
+    for k in [int(x) for x in args.strides.split(",")]:
+        ids = np.arange(0, npix, k, dtype=np.uint32)
+        n = int(ids.size)
+        ids_d[:n] = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        torch.cuda.synchronize()
+        auto = FAMILY_NAMES[rt_amd.render_pixels_path(sc, w, h, spp, n)[0]]
+        for fam in fams:
+            t_list, t_full = _timed_pair(listed(n, fam), full, args.reps)
+            times[(n, fam)] = t_list
+            log(f"{k:10d} {n:9d}  {FAMILY_NAMES[fam]:6s} {t_list:9.3f} {t_full:9.3f} {n * spp / t_list / 1e3:10.1f} "
+                f"{npix * spp / t_full / 1e3:10.1f} {t_list / t_full:14.3f}  {auto}")
+    if args.family == "both" and pool != rt_amd.LIST_FUSED:
+        ns = sorted({n for n, _ in times})
+        slower = [n for n in ns if times[(n, pool)] > times[(n, rt_amd.LIST_FUSED)]]
+        ok = [n for n in ns if not slower or n > max(slower)]
+        log(f"the pool is slower than k_render_list_f64 at n_pixels in {slower}; never slower from "
+            + (f"{min(ok)} on" if ok else "no measured length on"))
+
+
 def cmd_time(args):
     if rt_amd.device_count() < 1:
         raise RuntimeError("adapt_probe: no HIP device visible (it measures on the GPU only)")
+    if args.scene != "cornell_box" or args.family != "auto":
+        return cmd_time_families(args)
     log = Log(args.log)
     w, h = _size(args.size)
     npix, spp = w * h, 16
@@ -215,6 +277,9 @@ def main():
     t = sp.add_parser("time")
     t.add_argument("--size", default="1920x1080")
     t.add_argument("--reps", type=int, default=30)
+    t.add_argument("--scene", default="cornell_box", choices=SCENES)
+    t.add_argument("--family", default="auto", choices=("auto", "fused", "pool", "both"))
+    t.add_argument("--strides", default="1,2,10,100,1000", help="with --scene / --family: list k = every k-th pixel")
     t.add_argument("--log", default=os.path.join(REPO, "profiles", "adapt_time.log"))
     t.set_defaults(fn=cmd_time)
     g = sp.add_parser("target")

@@ -6,9 +6,10 @@ Accumulator.fill, which samples only the pixels without history (and a refresh p
       set-up: 96 x 72, src holds 16 passes of 16 spp, max_n = 64, moves A and B, the three scenes. Per flow: camera
       samples per view and the linear RMSE of the pixel colour against a 1024-spp frame of the view over all / valid /
       hole pixels; then the same over an orbit of --orbit views, each reprojected from the one before.
-  python tools/fill_probe.py time [--width 1920 --height 1080] [--out profiles/fill_probe.log]
+  python tools/fill_probe.py time [--width 1920 --height 1080] [--flows full,8/0,16/0,16/4] [--out profiles/fill_probe.log]
       One MI355X: the per-view time (reprojection + passes) of both flows, §14's protocol: host clocks around calls
       that wait for the device, one warm-up, best and median of --reps; and the RMSE against a --ref-spp frame.
+      --flows keeps only the named rows (full: the two full passes; F/R: fill F spp, refresh R), as DESIGN.md §16's re-run.
 A list render of seed s is the full frame's render of seed s at the listed pixels (rt_render_pixels' contract), so the
 CPU study renders every pass once as a full frame and gathers."""
 import argparse
@@ -172,7 +173,10 @@ def gpu_time(a):
             s1, s2 = pass_seed(SEED, 16), pass_seed(SEED, 17)
             dst.reproject_from(src, view, base, MAX_N)
             hist = dst.counts()[1] > 0  # the pixels that receive history
+            keep = set(a.flows.split(",")) if a.flows else None
             for label, flow in flows():
+                if keep is not None and ("full" if flow is None else f"{flow[0]}/{flow[1]}") not in keep:
+                    continue
                 t_rep, t_fill, lens = [], [], (npix, npix)
                 for rep in range(a.reps + 1):
                     t0 = time.perf_counter()
@@ -208,6 +212,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--orbit", type=int, default=8)
     ap.add_argument("--ref-spp", type=int, default=1024)
+    ap.add_argument("--flows", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.mode == "quality":
