@@ -53,7 +53,7 @@ pub const RT_FLAG_MESH_NEAREST: u32 = 1 << 3;
 
 /// The kernel family of a pixel-list render (`rt_render_pixels_with`, `rt_render_pixels_path`).
 pub const RT_LIST_AUTO: i32 = 0;
-/// `k_render_list_f64`, the fused per-lane walk.
+/// `k_render_list_f64`, the fused megakernel's list instance (per-lane walks).
 pub const RT_LIST_FUSED: i32 = 1;
 /// The flat-octree query pool's list instance.
 pub const RT_LIST_FPOOL: i32 = 2;

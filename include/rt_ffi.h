@@ -292,7 +292,7 @@ int rt_denoise_var_device(int32_t device, int32_t width, int32_t height, const d
  * (row 0 = top), strictly ascending, each < width * height. params must be the whole frame, as rt_accum_add requires
  * it: x0 = y0 = 0, tile_w = width, tile_h = height, row_step 0 or 1. Entry e of the outputs is pixel pixels[e]:
  * sub_out[e] (12 f64) is rt_render's sub_out of that pixel for the same seed, spp and flags, bit for bit, and
- * rgb_out[e] its RGB8, byte for byte. The f64 fused megakernel's per-vertex code runs it (k_render_list_f64), or, for
+ * rgb_out[e] its RGB8, byte for byte. The f64 fused megakernel's own body runs it (its list instance k_render_list_f64), or, for
  * a mesh scene whose full frame runs a pool kernel, that kernel's pixel-list instance (rt_render_pixels_path names the
  * family; the bits are the same whichever runs):
  * RT_FLAG_MIS passes through, RT_FLAG_MEGAKERNEL is implied; RT_FLAG_FP32 and RT_FLAG_MESH_NEAREST are out of scope
@@ -310,7 +310,7 @@ int rt_render_pixels_device(const rt_scene* scene, const rt_render_params* param
 
 /* The kernel family of a pixel-list render. */
 #define RT_LIST_AUTO  0
-#define RT_LIST_FUSED 1   /* k_render_list_f64 */
+#define RT_LIST_FUSED 1   /* k_render_list_f64, the fused megakernel's list instance */
 #define RT_LIST_FPOOL 2   /* the flat-octree query pool */
 #define RT_LIST_ROLES 3   /* the role-split pool */
 /* path_out[0]: the kernel family rt_render_pixels takes for this scene, these params and a list of n_pixels;

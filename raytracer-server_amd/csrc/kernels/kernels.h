@@ -77,11 +77,11 @@ int diag_read_flat(unsigned long long* cnt16, unsigned long long* reg32, unsigne
 hipError_t launch_megakernel_f32(const DevScene& sc, const RenderArgs& a, double* sub_buf, uint32_t* next_sub,
                                  hipStream_t st);
 hipError_t launch_finalize_f64(const RenderArgs& a, const double* sub_buf, hipStream_t st);
-// Pixel-list render (render_list_f64.hip): the subpixel means of the n_pixels frame pixels
+// Pixel-list render (render_f64.hip): the subpixel means of the n_pixels frame pixels
 // pixels[e] = row * width + col (device, unique ids < width * height) into sub_buf[e][4][3]; a.tw / th / x0 / y0 /
 // row_step play no part. n_pixels * 4 <= INT32_MAX. next_unit: the ticket counter (reset here).
-// family (include/rt_ffi.h RT_LIST_*): kListFused runs k_render_list_f64, the fused megakernel's per-vertex code
-// and Cfg choice (a.features & 15); kListFpool / kListRoles run the list instances of the frame's pool kernels
+// family (include/rt_ffi.h RT_LIST_*): kListFused runs k_render_list_f64, the list instance of the fused megakernel's
+// body with its Cfg choice (a.features & 15); kListFpool / kListRoles run the list instances of the frame's pool kernels
 // (launch_render_list_flat_f64 / launch_render_list_roles_f64), which must be list_pool_family's answer for the
 // scene (hipErrorInvalidValue otherwise); tail_buf / tail_cap: their split-tail scratch, as launch_megakernel_f64's.
 enum : int { kListFused = 1, kListFpool = 2, kListRoles = 3 };

@@ -1,6 +1,10 @@
 // f64 render kernels for gfx950 (CDNA4).
 //
 //   k_megakernel_f64  — fused, persistent path loop (below); k_finalize_f64 — subpixel means -> RGB8.
+//   k_render_list_f64 — the same loop over a list of frame pixels: analytic scenes, and mesh scenes
+//                       whose frame kernel has no list instance (Phong mesh scenes, octrees without slot tables) or
+//                       whose list is short; launch_render_list_f64 hands the other mesh scenes' lists to the list
+//                       instances of the frame's own pool kernels, which give the same bits.
 //   k_trace_f64       — Scene::trace_ray for a batch of rays (parity tests of the intersectors).
 //   wavefront kernels — see wavefront_f64.hip.
 #include <hip/hip_runtime.h>
@@ -48,15 +52,29 @@ typedef __attribute__((address_space(3))) uint64_t LdsU64;
 // Diagnostic builds (RT_DEBUG_TIMERS): each wave of k_megakernel_f64 records, on the constant 100 MHz clock
 // (s_memrealtime), when it started, when fewer than half of its lanes last held work (-1: never), and when it
 // ended (rt_debug_wave_times, tools/end_probe.py --waves): the end phase of a launch, wave by wave.
+// Both instance kinds of the body write them: after a k_render_list_f64 launch the records are that launch's.
 #if RT_DEBUG_TIMERS
 constexpr int kDbgWaves = 8192;
 constexpr int kDbgWaveRec = 5;
 __device__ unsigned long long g_dbg_wave[kDbgWaveRec * kDbgWaves];
 #endif
 
-template <int F, int W>
-__global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
-                                                          uint32_t* next_sub, long nsub, int refill) {
+// The loop's body, shared by its frame instances (L = false: k_megakernel_f64, units are the tile's subpixels) and
+// its pixel-list instances (L = true: k_render_list_f64, unit 4 e + j is subpixel j of the frame pixel pixels[e];
+// DESIGN.md §13). Everything but the camera sample's SubPixel works on the compact unit id; a list launch plans no
+// split tail (nsub == a.n_whole).
+// L adds a register with the pixel id of the unit in hand, pix = pixels[id >> 2], loaded where a lane's id enters a
+// list entry (load_pix: a new ticket, or a run crossing to (id & 3) == 0), and makes "this unit is whole" a
+// compile-time fact at its two uses, so a list instance holds no tail code. Both answer measurements against the
+// former copy of this loop (profiles/fused_list_fold_*.log): with pixels[] read at every camera sample
+// (unit_subpixel<L>, as the pool kernels do) and the tail tests left to run, the full lists ran 0.6% (cornell) and
+// 1.7% (cubes) slower; with the register alone 0.9% and 0.4%. Every read is made by an active lane: it holds a
+// ticket < nunits, so its id < n_whole = 4 n_pixels. (unit_of also runs for a lane whose ticket is past the end, or
+// -1 after a stop: that id is out of range, but the lane is inactive from then on and load_pix(active) reads nothing.)
+template <int F, bool L>
+__device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
+                                           uint32_t* next_sub, long nsub, int refill,
+                                           const uint32_t* __restrict__ pixels) {
     // Compact scenes (<= kMaxCompactObjects objects): the object table is copied into LDS, so the
     // shading's per-lane object reads (hit object, light) are ds_reads instead of global loads.
     // the fused mesh instances (F odd) keep the one-ballot guards (path_f64.h kCfgGuards1: they sit at their
@@ -98,6 +116,13 @@ __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, Render
         unit_of(a, t0, id, end_unused, s);
     }
     bool active = t0 < nunits;
+    [[maybe_unused]] uint32_t pix = 0;
+    const auto load_pix = [&](bool want) {
+        if constexpr (L) {
+            if (want) pix = pixels[id >> 2];
+        }
+    };
+    load_pix(active);
     acc_l[0] = 0.0; acc_l[256] = 0.0; acc_l[512] = 0.0;
     PathState ps;
     bool fresh = true;
@@ -133,11 +158,15 @@ __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, Render
         // lane needs a sample now or >= refill lanes have a free slot
         {
             const bool now = active && fresh;
-            const bool need = active && !fresh && nbuf < kCamDepth && unit_has(a, id, s, s + nbuf + 1);
+            const bool need = active && !fresh && nbuf < kCamDepth &&
+                              (L ? s + nbuf + 1 < a.n_samples : unit_has(a, id, s, s + nbuf + 1));
             if (__any(now) || (refill > 0 && __popcll(__ballot(need)) >= refill)) {
                 if (now || (refill > 0 && need)) {
                     RT_DBG_REGION(3);
-                    const CameraSample nb = camera_sample<C::g1>(sc, a, subpixel_of(a, id), now ? s : s + nbuf + 1);
+                    SubPixel sp;
+                    if constexpr (L) sp = subpixel_of_pixel(a, pix, id);
+                    else sp = subpixel_of(a, id);
+                    const CameraSample nb = camera_sample<C::g1>(sc, a, sp, now ? s : s + nbuf + 1);
                     if (now) {
                         begin_path(sc, nb, ps);
                         fresh = false;
@@ -165,7 +194,7 @@ __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, Render
             RT_DBG_TSTART(t_se);
             if (fresh) {
                 RT_DBG_REGION(4);
-                if (id < a.n_whole) {
+                if (L || id < a.n_whole) {  // (a list's units are all whole: its instances hold no tail code)
                     V3 acc = v3(acc_l[0], acc_l[256], acc_l[512]);
                     acc = acc + ps.L * a.inv_n;  // server.rs:357-358
                     acc_l[0] = acc.x; acc_l[256] = acc.y; acc_l[512] = acc.z;
@@ -176,6 +205,7 @@ __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, Render
                         o[2] = acc.z;
                         if (id + 1 < run_end(a, id)) {  // the next subpixel of the run, no ticket
                             ++id;
+                            load_pix((id & 3) == 0);
                             s = 0;
                             acc_l[0] = 0.0; acc_l[256] = 0.0; acc_l[512] = 0.0;
                             nbuf = 0;
@@ -237,6 +267,7 @@ __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, Render
             int end_unused;
             unit_of(a, nt, id, end_unused, s);
             active = !stop && nt < nunits;
+            load_pix(active);
             acc_l[0] = 0.0; acc_l[256] = 0.0; acc_l[512] = 0.0;
             fresh = true;
             nbuf = 0;
@@ -273,6 +304,19 @@ __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, Render
     }
 #endif
     RT_DBG_TFLUSH();
+}
+
+template <int F, int W>
+__global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
+                                                          uint32_t* next_sub, long nsub, int refill) {
+    fused_body<F, false>(sc_g, a_g, sub_buf, next_sub, nsub, refill, nullptr);
+}
+// The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
+template <int F, int W>
+__global__ __launch_bounds__(256, W) void k_render_list_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
+                                                           uint32_t* next_sub, long nsub, int refill,
+                                                           const uint32_t* __restrict__ pixels) {
+    fused_body<F, true>(sc_g, a_g, sub_buf, next_sub, nsub, refill, pixels);
 }
 
 // Split tail: subpixel n_whole + j's mean, continuing the sequential sum chunk 0 left in sub_buf (its lane
@@ -414,36 +458,65 @@ hipError_t launch_diag_fused(const DevScene& sc, const DiagArgs& a, bool visible
 
 thread_local TailPlan t_tail_plan;
 
-template <int F, int W>
+// One launch of the fused body. A frame (L = false) plans its split tail and sums it afterwards; a pixel list
+// (L = true: nsub = a.n_whole = 4 n_pixels) is handed out in runs of whole units only, with no split tail.
+template <int F, int W, bool L>
 static void launch_mk(const DevScene& sc, const RenderArgs& a_in, double* sub_buf, uint32_t* next_sub, long nsub,
-                      int refill, double* tail_buf, size_t tail_cap, hipStream_t st) {
-    const long blocks = resident_blocks(k_megakernel_f64<F, W>, (nsub + 255) / 256);
+                      int refill, double* tail_buf, size_t tail_cap, const uint32_t* pixels, hipStream_t st) {
     RenderArgs a = a_in;
-    plan_tail(a, nsub, blocks * 256, tail_buf, tail_cap, tail_split_x2(nsub, blocks * 256), 2, 256, RT_MK_MIN_RUN);
-    hipLaunchKernelGGL((k_megakernel_f64<F, W>), dim3((unsigned)blocks), dim3(256), 0, st, sc, a, sub_buf, next_sub, nsub,
-                       refill);
-    const long n_split = nsub - a.n_whole;
-    if (n_split > 0) {
-        const long tb = std::max(1L, std::min(4096L, (n_split + 255) / 256));
-        hipLaunchKernelGGL(k_tail_sum_f64, dim3((unsigned)tb), dim3(256), 0, st, a, sub_buf, n_split);
+    if constexpr (L) {
+        const long blocks = resident_blocks(k_render_list_f64<F, W>, (nsub + 255) / 256);
+        plan_units(a, blocks * 256, 256, RT_MK_MIN_RUN);
+        hipLaunchKernelGGL((k_render_list_f64<F, W>), dim3((unsigned)blocks), dim3(256), 0, st, sc, a, sub_buf, next_sub,
+                           nsub, refill, pixels);
+    } else {
+        const long blocks = resident_blocks(k_megakernel_f64<F, W>, (nsub + 255) / 256);
+        plan_tail(a, nsub, blocks * 256, tail_buf, tail_cap, tail_split_x2(nsub, blocks * 256), 2, 256, RT_MK_MIN_RUN);
+        hipLaunchKernelGGL((k_megakernel_f64<F, W>), dim3((unsigned)blocks), dim3(256), 0, st, sc, a, sub_buf, next_sub,
+                           nsub, refill);
+        launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
     }
 }
 
 // The analytic / fused-mesh megakernel at its waves/SIMD: 4 for analytic scenes, 3 with meshes (the defaults);
-// A/B builds (ab_knobs.h) compile both shapes of every instance for RT_MK_WAVES.
-template <int F>
+// A/B builds (ab_knobs.h) compile both shapes of every frame instance for RT_MK_WAVES.
+template <int F, bool L>
 static void launch_mk_shape(int waves, const DevScene& sc, const RenderArgs& a, double* sub_buf, uint32_t* next_sub,
-                            long nsub, int refill, double* tail_buf, size_t tail_cap, hipStream_t st) {
-    if constexpr (RT_AB_KNOBS != 0) {
-        if (waves == 3) launch_mk<F, 3>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, st);
-        else launch_mk<F, RT_MK_W4>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, st);
+                            long nsub, int refill, double* tail_buf, size_t tail_cap, const uint32_t* pixels,
+                            hipStream_t st) {
+    (void)waves;
+    if constexpr (RT_AB_KNOBS != 0 && !L) {
+        if (waves == 3) launch_mk<F, 3, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);
+        else launch_mk<F, RT_MK_W4, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);
     } else if constexpr ((F & 1) != 0) {
-        (void)waves;
-        launch_mk<F, 3>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, st);
+        launch_mk<F, 3, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);
     } else {
-        (void)waves;
-        launch_mk<F, RT_MK_W4>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, st);
+        launch_mk<F, RT_MK_W4, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);
     }
+}
+
+// camera-sample buffer refill threshold (lanes per wave; 0 disables the buffer)
+// (24 until round 2; 32-48 measured +0.6-0.9% on cornell, profiles/r02_ab.log)
+static int cam_refill() {
+    static const int refill = env_int("RT_MK_CAM_REFILL", 40);
+    return refill;
+}
+
+// The fused instance of a.features & 15, for a frame or a pixel list.
+template <bool L>
+static void launch_mk_features(int waves, const DevScene& sc, const RenderArgs& a, double* sub_buf, uint32_t* next_sub,
+                               long nsub, double* tail_buf, size_t tail_cap, const uint32_t* pixels, hipStream_t st) {
+    const int refill = cam_refill();
+#define RT_MK_CASE(F)                                                                                              \
+    case F:                                                                                                        \
+        launch_mk_shape<F, L>(waves, sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);      \
+        break;
+    switch (a.features & 15) {
+        RT_MK_CASE(0) RT_MK_CASE(1) RT_MK_CASE(2) RT_MK_CASE(3) RT_MK_CASE(4) RT_MK_CASE(5) RT_MK_CASE(6)
+        RT_MK_CASE(7) RT_MK_CASE(8) RT_MK_CASE(9) RT_MK_CASE(10) RT_MK_CASE(11) RT_MK_CASE(12) RT_MK_CASE(13)
+        RT_MK_CASE(14) RT_MK_CASE(15)
+    }
+#undef RT_MK_CASE
 }
 
 hipError_t launch_megakernel_f64(const DevScene& sc, const RenderArgs& a_in, double* sub_buf, uint32_t* next_sub,
@@ -467,9 +540,7 @@ hipError_t launch_megakernel_f64(const DevScene& sc, const RenderArgs& a_in, dou
     // 59 KB of LDS per block; 0 selects the fused per-vertex traversal for A/B runs). Shallow octrees (cubes: 9 nodes) walk in a few
     // steps: the fused traversal is faster there (profiles/r01_interleave_ab.log).
     static const int interleave = env_int("RT_MK_INTERLEAVE", 64);
-    // camera-sample buffer refill threshold (lanes per wave; 0 disables the buffer)
-    // (24 until round 2; 32-48 measured +0.6-0.9% on cornell, profiles/r02_ab.log)
-    static const int refill = env_int("RT_MK_CAM_REFILL", 40);
+    const int refill = cam_refill();
     static const int wmin = std::max(1, env_int("RT_MK_WALK_MIN", 1));
     static const int bvh_fused = env_int("RT_MK_BVH_FUSED", 0);  // A/B: nearest-triangle mode without interleaving
     // scenes whose meshes are all flat octrees (the cubes): block-synchronous batched mesh queries
@@ -484,7 +555,7 @@ hipError_t launch_megakernel_f64(const DevScene& sc, const RenderArgs& a_in, dou
         // traversal inline, 3 waves/SIMD
 #define RT_MB_CASE(F)                                                                             \
     case F:                                                                                       \
-        launch_mk<F, 3>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, st);          \
+        launch_mk<F, 3, false>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, nullptr, st); \
         break;
         switch (a.features & 31) {
             RT_MB_CASE(17) RT_MB_CASE(19) RT_MB_CASE(21) RT_MB_CASE(23) RT_MB_CASE(25) RT_MB_CASE(27) RT_MB_CASE(29)
@@ -493,16 +564,35 @@ hipError_t launch_megakernel_f64(const DevScene& sc, const RenderArgs& a_in, dou
 #undef RT_MB_CASE
         return hipGetLastError();
     }
-#define RT_MK_CASE(F)                                                           \
-    case F:                                                                     \
-        launch_mk_shape<F>(waves, sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, st); \
-        break;
-    switch (a.features & 15) {
-        RT_MK_CASE(0) RT_MK_CASE(1) RT_MK_CASE(2) RT_MK_CASE(3) RT_MK_CASE(4) RT_MK_CASE(5) RT_MK_CASE(6)
-        RT_MK_CASE(7) RT_MK_CASE(8) RT_MK_CASE(9) RT_MK_CASE(10) RT_MK_CASE(11) RT_MK_CASE(12) RT_MK_CASE(13)
-        RT_MK_CASE(14) RT_MK_CASE(15)
+    launch_mk_features<false>(waves, sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, st);
+    return hipGetLastError();
+}
+
+// Pixel-list render. family kListFused: the fused body's list instance, with the frame's Cfg
+// choice, mesh instances at 3 waves/SIMD and analytic ones at RT_MK_W4; kListFpool / kListRoles: the list instances
+// of the scene's pool kernel. RT_FLAG_FP32 and RT_FLAG_MESH_NEAREST are out of scope (rt_api.cpp returns RT_E_INVAL).
+hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* pixels, long n_pixels,
+                                  double* sub_buf, uint32_t* next_unit, int family, double* tail_buf, size_t tail_cap,
+                                  hipStream_t st) {
+    if (n_pixels <= 0 || a_in.n_samples <= 0) return hipSuccess;
+    if (n_pixels > 0x7fffffffL / 4) return hipErrorInvalidValue;
+    RenderArgs a = a_in;
+    a.n_whole = (int32_t)(n_pixels * 4);  // every unit is a whole subpixel unless a pool launcher plans a split tail
+    a.chunk_lg = 0;
+    a.tail_cps = 1;
+    a.tail_buf = nullptr;
+    t_tail_plan = TailPlan{};
+    hipError_t e = hipMemsetAsync(next_unit, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    // a mesh scene's pool family (the kernel its full frame runs); a family the scene has no
+    // instance of is an error, never a quiet change of kernel
+    if (family != kListFused) {
+        if (family != list_pool_family(a, sc.node_slot != nullptr)) return hipErrorInvalidValue;
+        if (family == kListFpool)
+            return launch_render_list_flat_f64(sc, a, pixels, n_pixels, sub_buf, next_unit, tail_buf, tail_cap, st);
+        return launch_render_list_roles_f64(sc, a, pixels, n_pixels, sub_buf, next_unit, tail_buf, tail_cap, st);
     }
-#undef RT_MK_CASE
+    launch_mk_features<true>(0, sc, a, sub_buf, next_unit, a.n_whole, nullptr, 0, pixels, st);
     return hipGetLastError();
 }
 

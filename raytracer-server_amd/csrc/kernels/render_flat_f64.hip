@@ -873,13 +873,22 @@ __global__ __launch_bounds__(B, W) void k_megakernel_fpool_list_f64(DevScene sc_
     fpool_body<F, B, true>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, pixels);
 }
 
-template <int F, int W, int B = kBlk>
+// One launch of the query pool, with its split tail planned: a frame (L = false) or a pixel list (L = true: nsub =
+// 4 n_pixels compact units).
+template <int F, int W, int B, bool L>
 static void launch_fpool(const DevScene& sc, RenderArgs& a, double* sub_buf, uint32_t* next_sub, long nsub,
-                         double* tail_buf, size_t tail_cap, int pool_min, int refill, hipStream_t st) {
-    const long blocks = resident_blocks(k_megakernel_fpool_f64<F, W, B>, (nsub + B - 1) / B, B);
+                         double* tail_buf, size_t tail_cap, int pool_min, int refill, const uint32_t* pixels,
+                         hipStream_t st) {
+    long blocks;
+    if constexpr (L) blocks = resident_blocks(k_megakernel_fpool_list_f64<F, W, B>, (nsub + B - 1) / B, B);
+    else blocks = resident_blocks(k_megakernel_fpool_f64<F, W, B>, (nsub + B - 1) / B, B);
     plan_tail(a, nsub, blocks * B, tail_buf, tail_cap, tail_split_x2(nsub, blocks * B));
-    hipLaunchKernelGGL((k_megakernel_fpool_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                       next_sub, nsub, pool_min, refill);
+    if constexpr (L)
+        hipLaunchKernelGGL((k_megakernel_fpool_list_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
+                           next_sub, nsub, pool_min, refill, pixels);
+    else
+        hipLaunchKernelGGL((k_megakernel_fpool_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
+                           next_sub, nsub, pool_min, refill);
 }
 
 template <int F, int W>
@@ -891,95 +900,92 @@ static void launch_flat(const DevScene& sc, RenderArgs& a, double* sub_buf, uint
                        next_sub, nsub);
 }
 
+// query chunks of pool_min (see RT_FPOOL_READY): 56 on the cubes 1024 spp 1093.3 Msamples/s (48: 1085.6, 64: 1087.6,
+// 80: 1061.0, 96: 1037.1; MIS 1027.5 -> 1034.2 at 56; profiles/r06ar_ab_fpool_min.log, r06as_ab_fpool_min.log)
+static int fpool_min() {
+    static const int pool_min = env_int("RT_MK_FPOOL_MIN", 56);
+    return pool_min;
+}
+// camera-sample refill threshold of the query-pool kernel (no-mirror scenes): 16-24 lanes measured
+// best on the cubes (8: 736.9, 16: 747.2, 24: 745.2, 32: 737.3, 40: 730.9 Msamples/s; the analytic
+// kernel's `refill` is 40)
+static int fpool_refill() {
+    static const int refill = env_int("RT_MK_FPOOL_REFILL", 20);
+    return refill;
+}
+// Does the scene run the no-mirror instances (Cfg::nospec, the 1024-thread block shape)? No mirror and no Phong object.
+static bool fpool_nospec(const RenderArgs& a) {
+    static const int nospec = env_int("RT_MK_NOSPEC", 1);  // A/B: 0 = the mirror-capable kernel for every scene
+    return nospec && (a.features & 32) && !(a.features & 2);
+}
+
+// The product dispatch of the query pool, for a frame or a pixel list: F | 32 at RT_FPOOL_BLOCK for scenes without a
+// mirror or Phong object, F at 3 waves/SIMD otherwise, then the split tail's sum. Lists have no Phong instances.
+template <bool L>
+static hipError_t launch_fpool_product(const DevScene& sc, RenderArgs& a, double* sub_buf, uint32_t* next_sub, long nsub,
+                                       double* tail_buf, size_t tail_cap, const uint32_t* pixels, hipStream_t st) {
+    if (L && (a.features & 2)) return hipErrorInvalidValue;  // Phong scenes stay on k_render_list_f64
+#define RT_FPOOL_CASE(F, W, B, LL)                                                                                        \
+    case (F) & 15:                                                                                                        \
+        launch_fpool<F, W, B, LL>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), pixels, st); \
+        break;
+    if (fpool_nospec(a)) {
+        switch (a.features & 15) {
+            RT_FPOOL_CASE(9 | 32, RT_FPOOL_BLOCK / 256, RT_FPOOL_BLOCK, L)
+            RT_FPOOL_CASE(13 | 32, RT_FPOOL_BLOCK / 256, RT_FPOOL_BLOCK, L)
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (a.features & 15) {
+            RT_FPOOL_CASE(9, 3, kBlk, L) RT_FPOOL_CASE(13, 3, kBlk, L)
+            RT_FPOOL_CASE(11, 3, kBlk, false) RT_FPOOL_CASE(15, 3, kBlk, false)  // Phong: frames only (lists returned above)
+            default: return hipErrorInvalidValue;
+        }
+    }
+#undef RT_FPOOL_CASE
+    launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
+    return hipGetLastError();
+}
+
 // The flat-mesh megakernel (scenes whose meshes are all DevMesh::flat; octree mode).
-// RT_MK_FLAT_WAVES: waves/SIMD requested from the register allocator (2 or 3).
 hipError_t launch_megakernel_flat_f64(const DevScene& sc, const RenderArgs& a_in, double* sub_buf, uint32_t* next_sub,
                                       double* tail_buf, size_t tail_cap, int refill, hipStream_t st) {
     const long nsub = (long)a_in.tw * a_in.th * 4;
     RenderArgs a = a_in;
-    static const int waves = env_int("RT_MK_FLAT_WAVES", 3);
-    static const int fpool = env_int("RT_MK_FPOOL", 1);
-    // query chunks of pool_min (see RT_FPOOL_READY): 56 on the cubes 1024 spp 1093.3 Msamples/s (48: 1085.6, 64: 1087.6,
-    // 80: 1061.0, 96: 1037.1; MIS 1027.5 -> 1034.2 at 56; profiles/r06ar_ab_fpool_min.log, r06as_ab_fpool_min.log)
-    static const int pool_min = env_int("RT_MK_FPOOL_MIN", 56);
-    static const int nospec = env_int("RT_MK_NOSPEC", 1);  // A/B: 0 = the mirror-capable kernel for every scene
-    // camera-sample refill threshold of the query-pool kernel (no-mirror scenes): 16-24 lanes measured
-    // best on the cubes (8: 736.9, 16: 747.2, 24: 745.2, 32: 737.3, 40: 730.9 Msamples/s; the analytic
-    // kernel's `refill` is 40)
-    static const int fpool_refill = env_int("RT_MK_FPOOL_REFILL", 20);
     (void)refill;
     // Product builds: the query pool at 3 waves/SIMD. The block-synchronous flat kernel (RT_MK_FPOOL=0) and the
-    // 2-wave shapes exist only in A/B builds (ab_knobs.h).
+    // 2-wave shapes (RT_MK_FLAT_WAVES=2: waves/SIMD requested from the register allocator) exist only in A/B builds
+    // (ab_knobs.h), and only for frames.
 #if RT_AB_KNOBS
-#define RT_FLAT_CASE(F)                                                                       \
-    case F:                                                                                   \
-        if (fpool) {                                                                          \
-            if (waves == 2) launch_fpool<F, 2>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); \
-            else launch_fpool<F, 3>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); \
-        } else if (waves == 2) launch_flat<F, 2>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st); \
-        else launch_flat<F, 3>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st); \
+    static const int waves = env_int("RT_MK_FLAT_WAVES", 3);
+    static const int fpool = env_int("RT_MK_FPOOL", 1);
+    if (!fpool || (waves == 2 && !fpool_nospec(a))) {
+#define RT_FLAT_CASE(F)                                                                                                   \
+    case F:                                                                                                               \
+        if (fpool) launch_fpool<F, 2, kBlk, false>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), nullptr, st); \
+        else if (waves == 2) launch_flat<F, 2>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st);                   \
+        else launch_flat<F, 3>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st);                                   \
         break;
-#else
-#define RT_FLAT_CASE(F)                                                                       \
-    case F:                                                                                   \
-        (void)waves;                                                                          \
-        launch_fpool<F, 3>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); \
-        break;
-#endif
-    if (fpool && nospec && (a.features & 32) && !(a.features & 2)) {  // no mirror, no Phong object
-        switch (a.features & 15) {
-            case 9: launch_fpool<9 | 32, RT_FPOOL_BLOCK / 256, RT_FPOOL_BLOCK>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
-            case 13: launch_fpool<13 | 32, RT_FPOOL_BLOCK / 256, RT_FPOOL_BLOCK>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
         switch (a.features & 15) {
             RT_FLAT_CASE(9) RT_FLAT_CASE(11) RT_FLAT_CASE(13) RT_FLAT_CASE(15)
             default: return hipErrorInvalidValue;
         }
-    }
 #undef RT_FLAT_CASE
-    launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
-    return hipGetLastError();
-}
-
-template <int F, int W, int B = kBlk>
-static void launch_fpool_list(const DevScene& sc, RenderArgs& a, const uint32_t* pixels, double* sub_buf,
-                              uint32_t* next_sub, long nsub, double* tail_buf, size_t tail_cap, int pool_min, int refill,
-                              hipStream_t st) {
-    const long blocks = resident_blocks(k_megakernel_fpool_list_f64<F, W, B>, (nsub + B - 1) / B, B);
-    plan_tail(a, nsub, blocks * B, tail_buf, tail_cap, tail_split_x2(nsub, blocks * B));
-    hipLaunchKernelGGL((k_megakernel_fpool_list_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                       next_sub, nsub, pool_min, refill, pixels);
+        launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
+        return hipGetLastError();
+    }
+#endif
+    return launch_fpool_product<false>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, st);
 }
 
 // The query pool over a pixel list (kernels.h list_pool_family == kListFpool: flat octrees, no Phong
-// object): launch_megakernel_flat_f64's product instances and planning with nsub = 4 n_pixels compact units, the
-// split tail included. Called by launch_render_list_f64 after the ticket counter is reset.
+// object): the frame's product instances and planning with nsub = 4 n_pixels compact units, the split tail included.
+// Called by launch_render_list_f64 after the ticket counter is reset.
 hipError_t launch_render_list_flat_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* pixels, long n_pixels,
                                        double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
                                        hipStream_t st) {
-    const long nsub = n_pixels * 4;
     RenderArgs a = a_in;
-    static const int pool_min = env_int("RT_MK_FPOOL_MIN", 56);       // as launch_megakernel_flat_f64
-    static const int nospec = env_int("RT_MK_NOSPEC", 1);
-    static const int fpool_refill = env_int("RT_MK_FPOOL_REFILL", 20);
-    if (a.features & 2) return hipErrorInvalidValue;  // Phong scenes stay on k_render_list_f64
-    if (nospec && (a.features & 32)) {  // no mirror object: the 1024-thread block shape
-        switch (a.features & 15) {
-            case 9: launch_fpool_list<9 | 32, RT_FPOOL_BLOCK / 256, RT_FPOOL_BLOCK>(sc, a, pixels, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
-            case 13: launch_fpool_list<13 | 32, RT_FPOOL_BLOCK / 256, RT_FPOOL_BLOCK>(sc, a, pixels, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (a.features & 15) {
-            case 9: launch_fpool_list<9, 3>(sc, a, pixels, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
-            case 13: launch_fpool_list<13, 3>(sc, a, pixels, sub_buf, next_sub, nsub, tail_buf, tail_cap, pool_min, fpool_refill, st); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-    launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
-    return hipGetLastError();
+    return launch_fpool_product<true>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, st);
 }
 
 // rt_diag_trace / rt_diag_visible, the flat query pool's split of a query (RenderArgs::all_flat scenes): the

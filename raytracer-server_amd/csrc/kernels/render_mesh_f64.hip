@@ -1249,17 +1249,25 @@ __global__ __launch_bounds__(B, W) void k_megakernel_roles_list_f64(DevScene sc_
     roles_body<F, S, B, true>(sc_g, a_g, sub_buf, next_sub, nsub, pixels);
 }
 
-template <int F, bool S = (RT_WALK_TIGHT != 0)>
+// One launch of the role-split pool, its split tail planned and summed: a frame (L = false) or a pixel list (L = true:
+// nsub = 4 n_pixels compact units).
+template <int F, bool L, bool S = (RT_WALK_TIGHT != 0)>
 static void launch_roles(const DevScene& sc, const RenderArgs& a_in, double* sub_buf, uint32_t* next_sub, long nsub,
-                         double* tail_buf, size_t tail_cap, hipStream_t st) {
+                         double* tail_buf, size_t tail_cap, const uint32_t* pixels, hipStream_t st) {
     constexpr int B = RoleShape<Cfg<F>>::block, W = B / 256;  // one block per CU: B / 256 waves per SIMD
-    const long blocks = resident_blocks(k_megakernel_roles_f64<F, W, S>, (nsub + B - 1) / B, B);
+    long blocks;
+    if constexpr (L) blocks = resident_blocks(k_megakernel_roles_list_f64<F, W, S>, (nsub + B - 1) / B, B);
+    else blocks = resident_blocks(k_megakernel_roles_f64<F, W, S>, (nsub + B - 1) / B, B);
     RenderArgs a = a_in;
     // the split tail and ticket runs planned for the lanes that hold paths (one path slot per thread)
     // six subpixels per path slot; runs of whole subpixels of ~64 samples (plan_units)
     plan_tail(a, nsub, blocks * RoleLayout<Cfg<F>>::paths, tail_buf, tail_cap, 12, 1, 64);
-    hipLaunchKernelGGL((k_megakernel_roles_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf, next_sub,
-                       nsub);
+    if constexpr (L)
+        hipLaunchKernelGGL((k_megakernel_roles_list_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
+                           next_sub, nsub, pixels);
+    else
+        hipLaunchKernelGGL((k_megakernel_roles_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
+                           next_sub, nsub);
     launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
 }
 
@@ -1304,7 +1312,7 @@ hipError_t launch_megakernel_mesh_f64(const DevScene& sc, const RenderArgs& a, d
     case F:                                                                                    \
         if (!sc.node_slot) launch_mm<F, 2, 1, false>(sc, a, sub_buf, next_sub, nsub, pool_ksteps, wmin, pool_refill, pool_min, pool_vmin, tail_buf, tail_cap, st); \
         RT_MM_AB(F)                                                                            \
-        else launch_roles<F>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st);          \
+        else launch_roles<F, false>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, st); \
         break;
 #define RT_MMB_CASE(F)                                                                         \
     case F:                                                                                    \
@@ -1321,28 +1329,16 @@ hipError_t launch_megakernel_mesh_f64(const DevScene& sc, const RenderArgs& a, d
     return hipGetLastError();
 }
 
-template <int F, bool S = (RT_WALK_TIGHT != 0)>
-static void launch_roles_list(const DevScene& sc, const RenderArgs& a_in, const uint32_t* pixels, double* sub_buf,
-                              uint32_t* next_sub, long nsub, double* tail_buf, size_t tail_cap, hipStream_t st) {
-    constexpr int B = RoleShape<Cfg<F>>::block, W = B / 256;
-    const long blocks = resident_blocks(k_megakernel_roles_list_f64<F, W, S>, (nsub + B - 1) / B, B);
-    RenderArgs a = a_in;
-    plan_tail(a, nsub, blocks * RoleLayout<Cfg<F>>::paths, tail_buf, tail_cap, 12, 1, 64);  // as launch_roles
-    hipLaunchKernelGGL((k_megakernel_roles_list_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                       next_sub, nsub, pixels);
-    launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
-}
-
 // The role-split pool over a pixel list (kernels.h list_pool_family == kListRoles: compact scenes
-// with slot tables and an octree of >= 64 nodes, no Phong object): launch_roles' planning with nsub = 4 n_pixels
+// with slot tables and an octree of >= 64 nodes, no Phong object): launch_roles with nsub = 4 n_pixels
 // compact units, the split tail included. Called by launch_render_list_f64 after the ticket counter is reset.
 hipError_t launch_render_list_roles_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
                                         double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
                                         hipStream_t st) {
     if (!sc.node_slot) return hipErrorInvalidValue;  // octrees without slot tables stay on k_render_list_f64
     switch (a.features & 31) {
-        case 9: launch_roles_list<9>(sc, a, pixels, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, st); break;
-        case 13: launch_roles_list<13>(sc, a, pixels, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, st); break;
+        case 9: launch_roles<9, true>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, st); break;
+        case 13: launch_roles<13, true>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, st); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -1,6 +1,6 @@
-"""The pixel-list render (rt_render_pixels, k_render_list_f64) against rt_render: for the same seed, spp and flags, entry
-e of its outputs is rt_render's sub_out and RGB8 of pixel pixels[e], bit for bit and byte for byte. That equality is the
-kernel's specification."""
+"""The pixel-list render (rt_render_pixels; k_render_list_f64, the fused megakernel's body over a list) against rt_render:
+for the same seed, spp and flags, entry e of its outputs is rt_render's sub_out and RGB8 of pixel pixels[e], bit for bit
+and byte for byte. That equality is the kernel's specification."""
 import ctypes
 
 import numpy as np
@@ -81,6 +81,74 @@ def test_flying_unicorn(rt, gpu_scenes, frames):
     rgb_f, sub_f = frames("flying_unicorn", False, 8, w, h)
     rgb, sub, _ = rt.render_pixels(gpu_scenes["flying_unicorn"], w, h, ids, 8, SEED, want_sub=True)
     assert np.array_equal(_bits(sub), _bits(dref.gather(sub_f, ids))) and np.array_equal(rgb, dref.gather(rgb_f, ids))
+
+
+# The fused list instance is the only list path of Phong scenes and of scenes of more than kMaxCompactObjects (16)
+# objects: a 24x18 frame, lists of one pixel, 65 sorted random pixels and every pixel, at spp 8 and 36.
+FW, FH = 24, 18
+
+
+def _fused_lists():
+    ids = np.sort(np.random.default_rng(11).choice(FW * FH, size=65, replace=False))
+    return [x.astype(np.uint32) for x in (np.array([FW * 7 + 5]), ids, np.arange(FW * FH))]
+
+
+_LIGHT = dict(geom_kind=0, pos=[50.0, 70.0, 100.0], r=4.0, brdf_kind=0, k=[0.0, 0.0, 0.0], emitted=[50.0, 50.0, 50.0])
+_CAM = ([50.0, 52.0, 295.6], [0.0, -0.042612, -1.0])
+
+
+def _phong_scene(rt):
+    """A Phong floor and a Phong sphere before a diffuse wall, under a light: 4 objects (a compact scene)."""
+    return rt.Scene.from_desc(*_CAM, [
+        dict(geom_kind=1, pos=[0, 0, 0], n=[0, 1, 0], brdf_kind=2, phong_kd=0.5, phong_ks=0.3, phong_power=8,
+             color_d=[0.7, 0.6, 0.5], color_s=[1, 1, 1]),
+        dict(geom_kind=0, pos=[40, 15, 80], r=15, brdf_kind=2, phong_kd=0.2, phong_ks=0.7, phong_power=24,
+             color_d=[0.9, 0.3, 0.3], color_s=[1, 1, 1]),
+        dict(geom_kind=1, pos=[0, 0, 0], n=[0, 0, 1], brdf_kind=0, k=[0.75, 0.75, 0.75]), _LIGHT])
+
+
+def _spheres_scene(rt):
+    """A diffuse floor, 17 diffuse spheres and a light: 19 objects, past the compact tables."""
+    objs = [dict(geom_kind=1, pos=[0, 0, 0], n=[0, 1, 0], brdf_kind=0, k=[0.75, 0.75, 0.75])]
+    for i in range(17):
+        objs.append(dict(geom_kind=0, pos=[10.0 + 5.0 * i, 6.0 + 3.0 * (i % 4), 60.0 + 7.0 * (i % 5)], r=4.0 + (i % 3),
+                         brdf_kind=0, k=[0.3 + 0.04 * i, 0.6, 0.9 - 0.04 * i]))
+    return rt.Scene.from_desc(*_CAM, objs + [_LIGHT])
+
+
+def _phong_chair(rt, tmp_path):
+    """The Phong chair of test_gpu_parity.py's split-tail test: a deep octree over a Phong floor."""
+    from test_host_prep import extra_asset_scene
+
+    p = extra_asset_scene(tmp_path, "chair.obj")
+    text = open(p).read()
+    floor = '{ type = "diffuse", kd = [0.75, 0.75, 0.75] }\ngeometry = { type = "plane", pos = [0.0, 0.0, 0.0]'
+    assert floor in text
+    text = text.replace(floor, floor.replace('{ type = "diffuse", kd = [0.75, 0.75, 0.75] }',
+                                             '{ type = "phong", kd = 0.5, ks = 0.3, power = 8, color_d = [0.7, 0.6, '
+                                             '0.5], color_s = [1.0, 1.0, 1.0] }'))
+    open(p, "w").write(text)
+    return rt.Scene.from_toml(p)
+
+
+@pytest.mark.parametrize("kind,mis", (("phong", False), ("phong", True), ("spheres", False), ("spheres", True),
+                                      ("phong_chair", True)))
+def test_fused_only_scenes_equal_rt_render(rt, tmp_path, kind, mis):
+    """Cfg F = 10 / 14 (Phong, compact), 0 / 4 (17 spheres: not compact) and 15 (the Phong chair with MIS, whose frame
+    runs the role pool): the list's sub and RGB8 against rt_render's, bit for bit and byte for byte."""
+    if kind == "phong_chair":
+        sc = _phong_chair(rt, tmp_path)
+        assert rt.render_pixels_path(sc, FW, FH, 8, FW * FH, mis=True)[1] == rt.LIST_FUSED
+    else:
+        sc = _phong_scene(rt) if kind == "phong" else _spheres_scene(rt)
+    for spp in (8, 36):
+        rgb_f, sub_f, _ = rt.render(sc, FW, FH, spp, SEED, mis=mis, megakernel=True, want_sub=True)
+        assert rgb_f.max() > 50
+        for ids in _fused_lists():
+            rgb, sub, st = rt.render_pixels(sc, FW, FH, ids, spp, SEED, mis=mis, want_sub=True)
+            assert st["samples"] == ids.size * 4 * (spp // 4)
+            assert np.array_equal(_bits(sub), _bits(dref.gather(sub_f, ids))), (kind, mis, spp, ids.size)
+            assert np.array_equal(rgb, dref.gather(rgb_f, ids))
 
 
 def test_outputs_are_optional_and_spp_rounds_down(rt, gpu_scenes, frames):

@@ -10,7 +10,8 @@
   python tools/adapt_probe.py time --scene cubes|flying_unicorn [--family both|fused|pool|auto] [--log ...]
       DESIGN.md §16, the same protocol for one scene and chosen kernel families (rt_render_pixels_with_device): lists of
       every pixel and every 2nd, 10th, 100th and 1000th pixel (--strides) at 16 spp, each family's list render interleaved with
-      rt_render_device of the full frame; `both` runs k_render_list_f64 and the scene's pool side by side and reports the
+      rt_render_device of the full frame; `both` runs the fused megakernel's list instance (k_render_list_f64) and the
+      scene's pool side by side and reports the
       shortest list from which the pool is never slower (the automatic choice's threshold).
   python tools/adapt_probe.py target [--size 96x72] [--log profiles/adapt_target.log]
       The three scenes with abs_tol in {0.03, 0.04, 0.06}: two full 8-spp passes, up to 30 sparse passes of 16 spp; mean
