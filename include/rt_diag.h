@@ -95,6 +95,47 @@ int rt_diag_trace(const struct rt_scene* scene, int32_t device, int32_t form, ui
  * analytic object already blocks the segment), 0 for the fused forms. */
 int rt_diag_visible(const struct rt_scene* scene, int32_t device, int32_t form, uint32_t flags, int64_t n, const double* x,
                     const double* y, uint8_t* vis, uint32_t* near_mask);
+
+/* Batch path vertices through the integrator of one kernel family, one lane per vertex (tests/test_gpu_vertices.py
+ * compares every form with the CPU oracle's orc_vertex vertex by vertex). A lane loads the state a render lane would
+ * hold on arrival at the vertex, traces its ray with the form's trace_closest<C>, calls the form's shade_vertex
+ * (csrc/device/integrator_f64.h) and stores the state it would carry on. Rows (host arrays):
+ *   st[n][19]   ray origin, ray direction, beta, L, bemit, o (3 doubles each), pdf_prev
+ *   rng[n][2]   the sample's xoroshiro128++ state
+ *   dk[n][2]    depth, kind (0 camera vertex, 1 after a mirror bounce, 2 after a diffuse bounce)
+ * st_out / rng_out / dk_out: the same rows after the vertex (bemit and o as the form's Cold holds them; a row whose
+ * ray misses is unchanged; the stream's state is stored when Russian roulette passed, as in the render loops);
+ * info[n][4]: hit object (-1 miss), the returned continue flag, ShadowDefer::pending and ::meshes (0 for the fused
+ * forms). `form` names the instantiation, with the Cfg bits its render kernel takes for this scene and flags:
+ *   RT_DIAG_FUSED      shade_vertex<C> with RegCold and no deferral, C as k_trace_f64 chooses it (the mesh code
+ *                      compiled in) plus the scene's Phong bit and the MIS flag
+ *   RT_DIAG_FUSED_G0   the same through the even-F instance of a mesh-free scene
+ *   RT_DIAG_FUSED_G1   the same through the kCfgGuards1 instances of a scene with meshes
+ *   RT_DIAG_FUSED_LDS  the fused megakernel's own instantiation (render_f64.hip fused_body): the object table in LDS,
+ *                      the one-ballot guards for a scene with meshes, LdsCold on a [6][256] LDS column per thread
+ * The deferred-shadow forms trace with the form's split (rt_diag_trace), call shade_vertex with a ShadowDefer as the
+ * form's render kernel does, and resolve a pending shadow query the way that kernel family does: the form's walk
+ * of each mesh in ShadowDefer::meshes, occluded iff a hit has !(t + 0.001 >= dist); ShadowDefer::c is added to L iff
+ * no mesh occludes:
+ *   RT_DIAG_SPLIT_SLOTS  the walk pool's instantiation (render_mesh_f64.hip: the object table in LDS, RegCold, the
+ *                        shadow ray returned in the ShadowDefer), slot walks
+ *   RT_DIAG_SPLIT_ROLES  the roles pool's instantiation (the same with LdsQuerySink: the shadow ray written to LDS
+ *                        columns and read back from there), slot walks; rt_diag_vertex only
+ *   RT_DIAG_SPLIT_KIDS   k_wf_shade's instantiation (wavefront_f64.hip), node_kids walks of every mesh
+ *   RT_DIAG_SPLIT_FLAT   the query pool's instantiation (render_flat_f64.hip: its nospec bit for a scene without
+ *                        mirror or Phong objects, LdsCold otherwise, LdsQuerySink), the shadow ray read back from the
+ *                        LDS query columns and resolved with flat_query
+ * flags: RT_FLAG_MIS, and RT_FLAG_MESH_NEAREST for the fused forms but FUSED_G0 (rt_ffi.h). Compact scenes only; the
+ * split forms ask of the scene what they ask in rt_diag_trace. A null pointer, n < 0, an unknown form or flag, a
+ * form the scene does not admit: RT_E_INVAL; then n == 0: RT_OK; then no visible HIP device: RT_E_NODEVICE. */
+#define RT_DIAG_FUSED_LDS 6
+#define RT_DIAG_SPLIT_ROLES 7
+int rt_diag_vertex(const struct rt_scene* scene, int32_t device, int32_t form, uint32_t flags, int64_t n, const double* st,
+                   const uint64_t* rng, const int32_t* dk, double* st_out, uint64_t* rng_out, int32_t* dk_out,
+                   int32_t* info);
+/* The device sincos_2pi (csrc/device/path_f64.h: the path's sin and cos of 2 pi u) of n host doubles in [0, 2 pi].
+ * A null pointer or n < 0: RT_E_INVAL; then n == 0: RT_OK; then no visible HIP device: RT_E_NODEVICE. */
+int rt_diag_sincos(int32_t device, int64_t n, const double* x, double* s, double* c);
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,17 @@ static inline double powi(double b, int n) {
     return neg ? 1.0 / r : r;
 }
 
+// The libm calls of a path vertex (sin, cos, and the Phong specular lobe's two pow calls), each result moved by
+// -1 / 0 / +1 ulp (orc_vertex: how far a vertex's outputs move when libm is an ulp off; all zero: libm's own bits).
+struct Nudge {
+    int s = 0, c = 0, pa = 0, pb = 0;
+};
+static inline double nudged(double v, int k) {
+    return k == 0 ? v : std::nextafter(v, k > 0 ? INFINITY : -INFINITY);
+}
+static inline double nsin(double x, const Nudge& g) { return nudged(std::sin(x), g.s); }
+static inline double ncos(double x, const Nudge& g) { return nudged(std::cos(x), g.c); }
+
 struct Ray {
     V3 pos, dir;
 };
@@ -128,6 +139,7 @@ static inline void philox4x32_10(const uint32_t ctr_in[4], const uint32_t key_in
 struct Rng {
     uint64_t s0, s1;
     Rng() : s0(1), s1(0) {}
+    Rng(uint64_t a, uint64_t b) : s0(a), s1(b) {}  // a stream from its raw state
     Rng(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t sub) {
         uint32_t ctr[4] = {pixel, sample, 0u, sub};
         uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
@@ -396,42 +408,49 @@ static void create_local_coord(V3 n, V3* u, V3* v, V3* w) {  // scene.rs:112
     *u = norm(cross(base, *w));
     *v = cross(*w, *u);
 }
-static void brdf_sample(const Object& o, V3 n, V3 out, Rng& rng, V3* in, double* pdf) {  // scene.rs:56
+// *lobe (may be null): 0 the diffuse lobe, 1 a mirror, 2 / 3 / 4 Phong's diffuse lobe, specular lobe, absorption
+static void brdf_sample(const Object& o, V3 n, V3 out, Rng& rng, V3* in, double* pdf, const Nudge& g = Nudge(),
+                        int* lobe = nullptr) {  // scene.rs:56
     switch (o.brdf) {
         case BRDF_DIFFUSE: {
             double z = std::sqrt(rng.uniform());
             double r = std::sqrt(1.0 - z * z);
             double phi = 2.0 * PI * rng.uniform();
-            double x = r * std::cos(phi), y = r * std::sin(phi);
+            double x = r * ncos(phi, g), y = r * nsin(phi, g);
             V3 u, v, w;
             create_local_coord(n, &u, &v, &w);
             V3 i = norm(u * x + v * y + w * z);
             *in = i;
             *pdf = dot(n, i) * FRAC_1_PI;
+            if (lobe) *lobe = 0;
             return;
         }
         case BRDF_SPECULAR:
             *in = flip_across(out, n);
             *pdf = 1.0;
+            if (lobe) *lobe = 1;
             return;
         default: {
             double p = (double)o.ph_power;
             double u = rng.uniform();
             if (u < o.ph_kd) {
                 double xi1 = rng.uniform(), xi2 = rng.uniform();
-                V3 i = v3(std::sqrt(1. - xi1) * std::cos(2. * PI * xi2), std::sqrt(1. - xi1) * std::sin(2. * PI * xi2), std::sqrt(xi1));
+                V3 i = v3(std::sqrt(1. - xi1) * ncos(2. * PI * xi2, g), std::sqrt(1. - xi1) * nsin(2. * PI * xi2, g), std::sqrt(xi1));
                 *in = i;
                 *pdf = dot(n, i) * FRAC_1_PI;
+                if (lobe) *lobe = 2;
             } else if (o.ph_kd <= u && u < o.ph_kd + o.ph_ks) {
                 double xi1 = rng.uniform(), xi2 = rng.uniform();
-                V3 i = v3(std::sqrt(1. - std::pow(xi1, 2. / (p + 1.))) * std::cos(2. * PI * xi2),
-                          std::sqrt(1. - std::pow(xi1, 2. / (p + 1.))) * std::sin(2. * PI * xi2),
-                          std::pow(xi1, 1. / (p + 1.)));
+                V3 i = v3(std::sqrt(1. - nudged(std::pow(xi1, 2. / (p + 1.)), g.pa)) * ncos(2. * PI * xi2, g),
+                          std::sqrt(1. - nudged(std::pow(xi1, 2. / (p + 1.)), g.pa)) * nsin(2. * PI * xi2, g),
+                          nudged(std::pow(xi1, 1. / (p + 1.)), g.pb));
                 *in = i;
                 *pdf = (p + 1.) / (2. * PI) * powi(i.z, o.ph_power);
+                if (lobe) *lobe = 3;
             } else {
                 *in = v3(0, 0, 0);
                 *pdf = 1.0;
+                if (lobe) *lobe = 4;
             }
             return;
         }
@@ -491,17 +510,19 @@ static bool trace_ray(const Scene& s, const Ray& ray, Hit* nh) {  // scene.rs:27
 }
 
 // geometry.rs:573 Geometry::sample
-static void light_sample(const Scene& s, Rng& rng, V3* y, V3* ny, double* pdf) {
+// *tri (may be null): the triangle a mesh light picked, -1 for a sphere light
+static void light_sample(const Scene& s, Rng& rng, V3* y, V3* ny, double* pdf, const Nudge& g = Nudge(), int* tri = nullptr) {
     const Object& L = s.objects[s.light];
     if (L.geom == GEOM_SPHERE) {
         double xi1 = rng.uniform(), xi2 = rng.uniform();
         double z = 2. * xi1 - 1.;
-        double x = std::sqrt(1.0 - z * z) * std::cos(2. * PI * xi2);
-        double yy = std::sqrt(1.0 - z * z) * std::sin(2. * PI * xi2);
+        double x = std::sqrt(1.0 - z * z) * ncos(2. * PI * xi2, g);
+        double yy = std::sqrt(1.0 - z * z) * nsin(2. * PI * xi2, g);
         V3 n = norm(v3(x, yy, z));
         *y = L.pos + n * L.r;
         *ny = n;
         *pdf = 1.0 / (4.0 * PI * L.r * L.r);
+        if (tri) *tri = -1;
         return;
     }
     if (L.geom == GEOM_MESH) {  // :588 WeightedIndex pick + Triangle::sample (missing +a: :622-635)
@@ -515,6 +536,7 @@ static void light_sample(const Scene& s, Rng& rng, V3* y, V3* ny, double* pdf) {
             acc += m.areas[i];
             if (acc > u) { idx = i; break; }
         }
+        if (tri) *tri = (int)idx;
         Tri t = m.tri(idx);
         double b0 = 1. - std::sqrt(rng.uniform());
         double b1 = (1. - b0) * rng.uniform();
@@ -555,6 +577,36 @@ struct Ctx {
 static const uint64_t MAX_BOUNCES = 5;         // scene.rs:109
 static const double SURVIVAL_PROBABILITY = 0.9;  // scene.rs:110
 
+// ---- the terms of scene.rs:161 reflected_radiance, shared by the recursion (reflected) and by one level of it
+// taken as a forward step (vertex_step, variant 0): the same expressions, so the same bits ----
+// Next-event estimation at x for the light sample (y, ny, pdf) with visibility vis (scene.rs:217-229); use_mis:
+// the light strategy of the balance heuristic, with the BSDF pdf of the direction (solid angle).
+static V3 nee_term(const Scene& s, const Object& obj, V3 n, V3 o, V3 x, V3 y, V3 ny, double pdf, double vis, bool use_mis) {
+    const Object& L = s.objects[s.light];
+    V3 i = norm(y - x);
+    double r_sqr = dot(y - x, y - x);
+    if (!use_mis) return mult(L.emitted, brdf_eval(obj, n, o, i)) * vis * dot(n, i) * dot(ny, -i) / (r_sqr * pdf);
+    double cosl = dot(ny, -i);
+    double pdf_l = pdf * r_sqr / cosl;      // area -> solid angle
+    double pdf_b = dot(n, i) * FRAC_1_PI;   // cosine lobe (diffuse) pdf of i
+    if (vis > 0. && cosl > 0. && pdf_b > 0.) {
+        double w = pdf_l / (pdf_l + pdf_b);
+        return mult(L.emitted, brdf_eval(obj, n, o, i)) * dot(n, i) * (w / pdf_l);
+    }
+    return v3(0, 0, 0);
+}
+// BSDF strategy hitting the light at distance t2 with facing normal n2 along i: the balance-heuristic weight of its
+// emitted radiance.
+static double mis_bsdf_weight(const Scene& s, double pdf_brdf, V3 n2, V3 i, double t2) {
+    double cosl = dot(n2, -i);
+    double pdf_l = light_pdf_area(s) * (t2 * t2) / cosl;
+    return pdf_brdf / (pdf_brdf + pdf_l);
+}
+// a (.) f cos / (pdf p): the weight of what comes back along the sampled direction i (scene.rs:178-183, :236-240)
+static V3 bsdf_weighted(V3 a, const Object& obj, V3 n, V3 o, V3 i, double pdf, double p) {
+    return mult(a, brdf_eval(obj, n, o, i)) * dot(n, i) / (pdf * p);
+}
+
 // scene.rs:161 reflected_radiance (MIS branch scene.rs:188 is `if false` in the reference: the
 // live estimator is NEE with area sampling, restated here). `mis` selects the build-defined
 // balance-heuristic estimator, not a reference behaviour.
@@ -573,35 +625,19 @@ static V3 reflected(Ctx& c, const Hit& hit, V3 o, uint64_t depth) {
             Hit h2;
             c.casts++;
             if (trace_ray(s, Ray{x, i}, &h2)) {
-                rad = s.objects[h2.id].emitted + mult(reflected(c, h2, o, depth + 1), brdf_eval(obj, n, o, i)) * dot(n, i) / (pdf * p);
+                rad = s.objects[h2.id].emitted + bsdf_weighted(reflected(c, h2, o, depth + 1), obj, n, o, i, pdf, p);
             }
         }
         return rad;
     }
     V3 rad;
-    const Object& L = s.objects[s.light];
     const bool use_mis = c.mis && obj.brdf == BRDF_DIFFUSE;  // MIS defined for the diffuse lobe only
     {
         V3 y, ny; double pdf;
         light_sample(s, rng, &y, &ny, &pdf);
-        V3 i = norm(y - x);
-        double r_sqr = dot(y - x, y - x);
         c.casts++;
         double vis = mutually_visible(s, x, y) ? 1. : 0.;
-        if (!use_mis) {
-            rad = mult(L.emitted, brdf_eval(obj, n, o, i)) * vis * dot(n, i) * dot(ny, -i) / (r_sqr * pdf);
-        } else {
-            // light strategy, balance heuristic with the BSDF pdf of direction i (solid angle)
-            double cosl = dot(ny, -i);
-            double pdf_l = pdf * r_sqr / cosl;      // area -> solid angle
-            double pdf_b = dot(n, i) * FRAC_1_PI;   // cosine lobe (diffuse) pdf of i
-            if (vis > 0. && cosl > 0. && pdf_b > 0.) {
-                double w = pdf_l / (pdf_l + pdf_b);
-                rad = mult(L.emitted, brdf_eval(obj, n, o, i)) * dot(n, i) * (w / pdf_l);
-            } else {
-                rad = v3(0, 0, 0);
-            }
-        }
+        rad = nee_term(s, obj, n, o, x, y, ny, pdf, vis, use_mis);
     }
     if (rng.uniform() < p) {
         V3 i; double pdf_brdf;
@@ -612,17 +648,134 @@ static V3 reflected(Ctx& c, const Hit& hit, V3 o, uint64_t depth) {
             V3 rec = reflected(c, h2, -i, depth + 1);
             if (use_mis && h2.id == s.light) {
                 // BSDF strategy hitting the light: emitted radiance weighted by the balance heuristic
-                const Object& Lo = s.objects[s.light];
-                double cosl = dot(h2.n, -i);
-                double t2 = h2.t;
-                double pdf_l = light_pdf_area(s) * (t2 * t2) / cosl;
-                double w = pdf_brdf / (pdf_brdf + pdf_l);
-                rec = rec + Lo.emitted * w;
+                rec = rec + s.objects[s.light].emitted * mis_bsdf_weight(s, pdf_brdf, h2.n, i, h2.t);
             }
-            rad = rad + mult(rec, brdf_eval(obj, n, o, i)) * dot(n, i) / (pdf_brdf * p);
+            rad = rad + bsdf_weighted(rec, obj, n, o, i, pdf_brdf, p);
         }
     }
     return rad;
+}
+
+// ---- one vertex of the path as a forward step (orc_vertex) ----
+// The recursion above walked forward with throughput, as the device walks it (integrator_f64.h): beta is the
+// product of the f cos / (pdf p) so far, L the radiance gathered so far, and a vertex
+//   camera hit:  L  = Le(x)
+//   after a mirror bounce: L += bemit (.) Le(x)   (bemit: the beta before that bounce; `o` goes on unchanged)
+//   after a diffuse bounce under MIS, on the light, pdf_prev > 0: L += beta (.) Le(x) w
+//   then, not a mirror: L += beta (.) NEE;  Russian roulette;  beta (.)= f cos / (pdf p).
+// variant 0 writes every term with the expressions of `reflected` (the shared helpers above); variant 1 with the
+// device's algebraic forms (integrator_f64.h RT_OPT_NEE / RT_OPT_BETA / RT_OPT_LEF / RT_OPT_KPI), in plain IEEE
+// arithmetic: with equal libm results it is what a device lane must produce bit for bit.
+enum { K_CAMERA = 0, K_SPEC = 1, K_DIFF = 2 };
+struct VState {
+    Ray ray;
+    V3 beta, L, bemit, o;
+    double pdf_prev;
+    uint64_t r0, r1;
+    uint32_t depth;
+    int kind;
+};
+struct VInfo {
+    int hit;       // object, -1: miss
+    int cont;      // the path goes on: survived and (mirror or beta != 0)
+    int survived;  // Russian roulette passed (0 for a miss)
+    int lobe;      // brdf_sample's lobe (-1: none sampled)
+    int nee_vis;   // NEE: 1 visible, 0 occluded, -1 no NEE (miss, mirror), -2 skipped (variant 1: Le f == 0)
+    int light_tri; // the mesh light's picked triangle (-1: none)
+    double hit_t;
+    V3 x, y;       // the vertex and the light sample (NEE vertices)
+    V3 n, ny;      // their normals
+};
+static inline bool is_zero(V3 a) { return a.x == 0.0 && a.y == 0.0 && a.z == 0.0; }
+static void vertex_step(const Scene& s, bool mis, int variant, const Nudge& g, VState& ps, VInfo& vi) {
+    vi = VInfo{-1, 0, 0, -1, -1, -1, 0.0, v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0)};
+    Hit hit;
+    if (!trace_ray(s, ps.ray, &hit)) return;
+    vi.hit = hit.id;
+    vi.hit_t = hit.t;
+    const Object& obj = s.objects[hit.id];
+    const Object& Lo = s.objects[s.light];
+    V3 x = hit.pos, n = hit.n;
+    vi.x = x;
+    vi.n = n;
+    if (ps.kind == K_CAMERA) {
+        ps.L = obj.emitted;
+    } else if (ps.kind == K_SPEC) {
+        ps.L = ps.L + mult(ps.bemit, obj.emitted);
+    } else if (mis && hit.id == s.light && ps.pdf_prev > 0.0) {
+        double w;
+        if (variant == 0) {
+            w = mis_bsdf_weight(s, ps.pdf_prev, n, ps.ray.dir, hit.t);
+        } else {  // numerator and denominator times cosl: one division
+            const double cosl = dot(n, -ps.ray.dir);
+            const double pc = ps.pdf_prev * cosl;
+            w = pc / (pc + light_pdf_area(s) * (hit.t * hit.t));
+        }
+        ps.L = ps.L + mult(ps.beta, obj.emitted * w);
+    }
+    V3 o = ps.kind == K_SPEC ? ps.o : -ps.ray.dir;
+    ps.depth += 1;
+    const double p = ps.depth <= MAX_BOUNCES ? 1.0 : SURVIVAL_PROBABILITY;
+    Rng rng(ps.r0, ps.r1);
+    const bool spec = obj.brdf == BRDF_SPECULAR;
+    const bool use_mis = mis && obj.brdf == BRDF_DIFFUSE;
+    if (!spec) {
+        V3 y, ny; double pdfA;
+        light_sample(s, rng, &y, &ny, &pdfA, g, &vi.light_tri);
+        vi.y = y;
+        vi.ny = ny;
+        if (variant == 0) {
+            const double vis = mutually_visible(s, x, y) ? 1. : 0.;
+            vi.nee_vis = (int)vis;
+            ps.L = ps.L + mult(ps.beta, nee_term(s, obj, n, o, x, y, ny, pdfA, vis, use_mis));
+        } else {
+            const V3 diff = y - x;
+            const double r_sqr = dot(diff, diff);
+            const V3 i = diff / std::sqrt(r_sqr);
+            // Le f: for a diffuse vertex the host's product Le (kd / pi)
+            const V3 lef = obj.brdf == BRDF_DIFFUSE ? mult(Lo.emitted, obj.k * FRAC_1_PI) : mult(Lo.emitted, brdf_eval(obj, n, o, i));
+            vi.nee_vis = -2;
+            if (!is_zero(lef)) {
+                const double vis = mutually_visible(s, x, y) ? 1. : 0.;
+                vi.nee_vis = (int)vis;
+                V3 c;
+                if (!use_mis) {
+                    c = lef * (vis * dot(n, i) * dot(ny, -i) * (1.0 / (r_sqr * pdfA)));
+                } else {
+                    const double cosl = dot(ny, -i);
+                    const double pdf_l = pdfA * r_sqr / cosl;
+                    const double pdf_b = dot(n, i) * FRAC_1_PI;
+                    c = v3(0, 0, 0);
+                    // (pdf_l / (pdf_l + pdf_b)) / pdf_l == 1 / (pdf_l + pdf_b)
+                    if (vis > 0. && cosl > 0. && pdf_b > 0.) c = lef * (dot(n, i) * (1.0 / (pdf_l + pdf_b)));
+                }
+                ps.L = ps.L + mult(ps.beta, c);
+            }
+        }
+    }
+    if (!(rng.uniform() < p)) return;
+    vi.survived = 1;
+    V3 wi; double pdf;
+    brdf_sample(obj, n, o, rng, &wi, &pdf, g, &vi.lobe);
+    ps.r0 = rng.s0;
+    ps.r1 = rng.s1;
+    if (spec) {
+        ps.bemit = ps.beta;
+        ps.o = o;
+    }
+    const double cw = dot(n, wi);
+    if (variant == 1 && obj.brdf != BRDF_PHONG && cw != 0.0) {
+        // f cos / (pdf p) with cos and pdf cancelled: diffuse kd / p, mirror ks / p
+        ps.beta = mult(ps.beta, obj.k) * (ps.depth <= MAX_BOUNCES ? 1.0 : 1.0 / SURVIVAL_PROBABILITY);
+    } else if (variant == 1) {
+        ps.beta = mult(ps.beta, brdf_eval(obj, n, o, wi)) * cw / (pdf * p);
+    } else {
+        ps.beta = bsdf_weighted(ps.beta, obj, n, o, wi, pdf, p);
+    }
+    ps.ray = Ray{x, wi};
+    ps.kind = spec ? K_SPEC : K_DIFF;
+    ps.pdf_prev = use_mis ? pdf : 0.0;
+    vi.cont = (spec || !is_zero(ps.beta)) ? 1 : 0;
 }
 
 static V3 received(Ctx& c, const Ray& r) {  // scene.rs:152
@@ -632,6 +785,17 @@ static V3 received(Ctx& c, const Ray& r) {  // scene.rs:152
         return c.s->objects[h.id].emitted + reflected(c, h, -r.dir, 1);
     }
     return v3(0, 0, 0);
+}
+
+// The camera ray of subpixel (sx, sy) of pixel (x, y) (server.rs:339-357): two draws for the tent filter.
+static Ray camera_ray(const Scene& s, Rng& rng, V3 cx, V3 cy, double w, double h, int x, int y, int sx, int sy) {
+    double r1 = 2. * rng.uniform();
+    double dx = r1 < 1. ? std::sqrt(r1) - 1. : 1. - std::sqrt(2. - r1);
+    double r2 = 2. * rng.uniform();
+    double dy = r2 < 1. ? std::sqrt(r2) - 1. : 1. - std::sqrt(2. - r2);
+    V3 d = cx * ((((double)sx + 0.5 + dx) / 2. + (double)x) / w - 0.5) +
+           cy * ((((double)sy + 0.5 + dy) / 2. + (double)y) / h - 0.5) + s.camera.dir;
+    return Ray{s.camera.pos, norm(d)};
 }
 
 // server.rs:320 sample_pixel; writes the 4 subpixel means (before clamp) to sub_out[12].
@@ -649,13 +813,7 @@ static V3 sample_pixel(const Scene& s, int x, int y, int width, int height, int 
             const uint32_t sub = (uint32_t)(sy * 2 + sx);
             for (int smp = 0; smp < num_samples; ++smp) {
                 c.rng = Rng(seed, pixel_id, (uint32_t)smp, sub);
-                double r1 = 2. * c.rng.uniform();
-                double dx = r1 < 1. ? std::sqrt(r1) - 1. : 1. - std::sqrt(2. - r1);
-                double r2 = 2. * c.rng.uniform();
-                double dy = r2 < 1. ? std::sqrt(r2) - 1. : 1. - std::sqrt(2. - r2);
-                V3 d = cx * ((((double)sx + 0.5 + dx) / 2. + (double)x) / w - 0.5) +
-                       cy * ((((double)sy + 0.5 + dy) / 2. + (double)y) / h - 0.5) + s.camera.dir;
-                rad = rad + received(c, Ray{s.camera.pos, norm(d)}) * (1. / (double)num_samples);
+                rad = rad + received(c, camera_ray(s, c.rng, cx, cy, w, h, x, y, sx, sy)) * (1. / (double)num_samples);
             }
             if (sub_out) {
                 sub_out[(sy * 2 + sx) * 3 + 0] = rad.x;
@@ -952,6 +1110,102 @@ void orc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
 void orc_draws(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t sub, int n, double* out) {
     Rng r(seed, pixel, sample, sub);
     for (int k = 0; k < n; ++k) out[k] = r.uniform();
+}
+
+// The first n uniforms of the xoroshiro128++ stream with the raw state (s0, s1), and the state after them.
+void orc_stream(uint64_t s0, uint64_t s1, int n, double* out, uint64_t after[2]) {
+    Rng r(s0, s1);
+    for (int k = 0; k < n; ++k) out[k] = r.uniform();
+    if (after) { after[0] = r.s0; after[1] = r.s1; }
+}
+
+// glibc's sin and cos of n doubles.
+void orc_sincos(int64_t n, const double* x, double* s, double* c) {
+    for (int64_t i = 0; i < n; ++i) { s[i] = std::sin(x[i]); c[i] = std::cos(x[i]); }
+}
+
+// The triangle_selector weights of the light when it is a mesh (geometry.rs:588): areas[n] (may be null to ask for
+// n). Returns the triangle count, 0 for a sphere light.
+int64_t orc_light_areas(orc_scene_t* sc, double* areas) {
+    const Object& L = sc->s.objects[sc->s.light];
+    if (L.geom != GEOM_MESH) return 0;
+    const Mesh& m = sc->s.meshes[L.mesh];
+    if (areas) for (size_t i = 0; i < m.areas.size(); ++i) areas[i] = m.areas[i];
+    return (int64_t)m.areas.size();
+}
+
+// Path vertices as packed rows, the layout of orc_vertex and of the device's rt_diag_vertex:
+//   st[n][19]  ray origin, ray direction, beta, L, bemit, o (3 each), pdf_prev
+//   rng[n][2]  the xoroshiro128++ state;  dk[n][2]  depth, kind (0 camera, 1 after a mirror, 2 after a diffuse bounce)
+static VState vstate_load(const double* st, const uint64_t* rng, const int32_t* dk) {
+    VState p;
+    p.ray = Ray{v3(st[0], st[1], st[2]), v3(st[3], st[4], st[5])};
+    p.beta = v3(st[6], st[7], st[8]);
+    p.L = v3(st[9], st[10], st[11]);
+    p.bemit = v3(st[12], st[13], st[14]);
+    p.o = v3(st[15], st[16], st[17]);
+    p.pdf_prev = st[18];
+    p.r0 = rng[0]; p.r1 = rng[1];
+    p.depth = (uint32_t)dk[0]; p.kind = dk[1];
+    return p;
+}
+static void vstate_store(const VState& p, double* st, uint64_t* rng, int32_t* dk) {
+    const V3 v[6] = {p.ray.pos, p.ray.dir, p.beta, p.L, p.bemit, p.o};
+    for (int k = 0; k < 6; ++k) { st[3 * k] = v[k].x; st[3 * k + 1] = v[k].y; st[3 * k + 2] = v[k].z; }
+    st[18] = p.pdf_prev;
+    rng[0] = p.r0; rng[1] = p.r1;
+    dk[0] = (int32_t)p.depth; dk[1] = p.kind;
+}
+
+// The state a path holds on arrival at its first vertex: the camera ray of sample smp[i] of subpixel sub[i] of the
+// pixel (col[i], row[i]) of a width x height frame (RNG key row * width + col, as orc_render), beta 1, the stream
+// after the two camera draws.
+void orc_camera_states(orc_scene_t* sc, int width, int height, uint64_t seed, int64_t n, const int32_t* col,
+                       const int32_t* row, const int32_t* sub, const int32_t* smp, double* st, uint64_t* rng, int32_t* dk) {
+    const Scene& s = sc->s;
+    double w = (double)width, h = (double)height;
+    V3 cx = v3(w * 0.5135 / h, 0., 0.);
+    V3 cy = norm(cross(cx, s.camera.dir)) * 0.5135;
+    for (int64_t i = 0; i < n; ++i) {
+        Rng r(seed, (uint32_t)row[i] * (uint32_t)width + (uint32_t)col[i], (uint32_t)smp[i], (uint32_t)sub[i]);
+        VState p{};
+        p.ray = camera_ray(s, r, cx, cy, w, h, col[i], height - row[i] - 1, sub[i] & 1, sub[i] >> 1);
+        p.beta = v3(1, 1, 1);
+        p.r0 = r.s0; p.r1 = r.s1;
+        p.kind = K_CAMERA;
+        vstate_store(p, st + 19 * i, rng + 2 * i, dk + 2 * i);
+    }
+}
+
+// One vertex per row (vertex_step): traces the row's ray, shades the hit, writes the state the path carries on
+// (the same layout; st_out / rng_out / dk_out may alias the inputs). variant 0: the reference's expressions,
+// 1: the device's algebraic forms. nudge[4]: ulps (-1 / 0 / +1) added to the results of sin, cos and the Phong
+// specular lobe's pow(xi1, 2 / (p + 1)) and pow(xi1, 1 / (p + 1)).
+//   info[n][6]  hit object (-1 miss), continue flag, survived, BSDF lobe (0 diffuse, 1 mirror, 2 / 3 / 4 Phong diffuse /
+//               specular / absorbed, -1 none), NEE visibility (1 / 0, -1 no NEE, -2 skipped for Le f == 0), the
+//               mesh light's triangle (-1 none)
+//   aux[n][13]  hit t, the vertex x, the light sample y, the normals at x and at y (may be null)
+void orc_vertex(orc_scene_t* sc, int64_t n, int mis, int variant, const int32_t nudge[4], const double* st,
+                const uint64_t* rng, const int32_t* dk, double* st_out, uint64_t* rng_out, int32_t* dk_out,
+                int32_t* info, double* aux) {
+    Nudge g;
+    g.s = nudge[0]; g.c = nudge[1]; g.pa = nudge[2]; g.pb = nudge[3];
+    for (int64_t i = 0; i < n; ++i) {
+        VState p = vstate_load(st + 19 * i, rng + 2 * i, dk + 2 * i);
+        VInfo vi;
+        vertex_step(sc->s, mis != 0, variant, g, p, vi);
+        vstate_store(p, st_out + 19 * i, rng_out + 2 * i, dk_out + 2 * i);
+        int32_t* f = info + 6 * i;
+        f[0] = vi.hit; f[1] = vi.cont; f[2] = vi.survived; f[3] = vi.lobe; f[4] = vi.nee_vis; f[5] = vi.light_tri;
+        if (aux) {
+            double* a = aux + 13 * i;
+            a[0] = vi.hit_t;
+            a[1] = vi.x.x; a[2] = vi.x.y; a[3] = vi.x.z;
+            a[4] = vi.y.x; a[5] = vi.y.y; a[6] = vi.y.z;
+            a[7] = vi.n.x; a[8] = vi.n.y; a[9] = vi.n.z;
+            a[10] = vi.ny.x; a[11] = vi.ny.y; a[12] = vi.ny.z;
+        }
+    }
 }
 
 // Scene::trace_ray for a batch of rays: t, object id (-1 miss), hit pos[3], n[3].

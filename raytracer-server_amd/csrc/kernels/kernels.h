@@ -134,4 +134,40 @@ hipError_t launch_diag_kids(const DevScene& sc, const DiagArgs& a, bool visible,
 // render_flat_f64.hip: the flat query pool's split (analytic part, near mask, flat_query per near mesh)
 hipError_t launch_diag_flat(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st);
 
+
+// Batch vertex diagnostics (include/rt_diag.h rt_diag_vertex, kernels/diag_queries.h): n path vertices, one lane
+// each, as packed rows (device pointers): st[n][19] = ray origin, ray direction, beta, L, bemit, o, pdf_prev;
+// rng[n][2] the stream's state; dk[n][2] = depth, kind; the *_out rows: the state the lane carries on, bemit and o
+// as the form's Cold returns them; info[n][4] = hit object, continue flag, and for the deferred forms
+// ShadowDefer::pending and ::meshes.
+struct DiagVertexArgs {
+    long n;
+    const double* st;
+    const uint64_t* rng;
+    const int32_t* dk;
+    double* st_out;
+    uint64_t* rng_out;
+    int32_t* dk_out;
+    int32_t* info;
+};
+// render_f64.hip: trace_closest<C> and shade_vertex<C> (no deferral) for a compact scene with a.features' Phong and
+// MIS bits. guards 0: k_trace_f64's C (mesh code compiled in, RegCold); 1: the even-F mesh-free instance; 2: the
+// kCfgGuards1 mesh instances; 3: fused_body's own C (the object table in LDS, the one-ballot guards for a mesh
+// scene) with LdsCold on a [6][256] column per thread, as fused_body calls it. mesh_nearest: the BVH walks.
+hipError_t launch_diag_vertex_fused(const DevScene& sc, const RenderArgs& a, const DiagVertexArgs& v, int guards,
+                                    bool mesh_nearest, hipStream_t st);
+// The deferred-shadow forms: the form's split trace, shade_vertex with a ShadowDefer as the form's render kernel
+// calls it for a.features (hipErrorInvalidValue for features the kernel family has no instance of), then the
+// pending shadow query resolved as the family resolves it, defer.c added iff no mesh occludes.
+// render_mesh_f64.hip: the slot-walk pools (needs DevScene::node_slot). sink = false: the walk pool's call, the
+// shadow ray returned in the ShadowDefer; sink = true: the roles pool's, LdsQuerySink into LDS columns
+hipError_t launch_diag_vertex_slots(const DevScene& sc, const RenderArgs& a, const DiagVertexArgs& v, bool sink,
+                                    hipStream_t st);
+// wavefront_f64.hip: k_wf_shade's instantiation, node_kids walks
+hipError_t launch_diag_vertex_kids(const DevScene& sc, const RenderArgs& a, const DiagVertexArgs& v, hipStream_t st);
+// render_flat_f64.hip: the query pool's instantiation (its nospec bit, LdsCold, LdsQuerySink), flat_query
+hipError_t launch_diag_vertex_flat(const DevScene& sc, const RenderArgs& a, const DiagVertexArgs& v, hipStream_t st);
+// render_f64.hip: sincos_2pi (path_f64.h) of n doubles (device pointers).
+hipError_t launch_diag_sincos(long n, const double* x, double* s, double* c, hipStream_t st);
+
 }  // namespace rt

@@ -456,6 +456,80 @@ hipError_t launch_diag_fused(const DevScene& sc, const DiagArgs& a, bool visible
     return hipGetLastError();
 }
 
+// rt_diag_vertex, the fused forms: one path vertex per lane, trace_closest<C> then shade_vertex<C> with no
+// deferral (the shadow ray inline), as fused_body's iteration runs them. Cold = RegCold: bemit and o in the
+// PathState; Cold = LdsCold: fused_body's own instantiation, on a [6][256] LDS column per thread (the row's bemit
+// and o are written there first, and read back from there afterwards). C::ldsobj instances fill the LDS object
+// table first, every thread of the block taking part.
+template <int F, bool kLdsCold>
+__global__ __launch_bounds__(256) void k_diag_vertex_fused(DevScene sc, RenderArgs a, DiagVertexArgs v) {
+    using C = Cfg<F>;
+    if constexpr (C::ldsobj) lds_objects_fill(sc);
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= v.n) return;
+    PathState ps = diag_vertex_load(v, i);
+    const HitRec hr = trace_closest<C>(sc, ps.ray);
+    if constexpr (kLdsCold) {
+        __shared__ double s_cold[6 * 256];
+        const LdsCold cold{(LdsDouble*)s_cold + threadIdx.x};
+        cold.set_o(ps, ps.o);
+        cold.set_bemit(ps, ps.bemit);
+        const bool cont = shade_vertex<C>(sc, a, ps, hr, nullptr, cold);
+        diag_vertex_store(v, i, ps, cold.bemit(ps), cold.o(ps), hr.obj, cont, false, 0u);
+    } else {
+        const bool cont = shade_vertex<C>(sc, a, ps, hr);
+        diag_vertex_store(v, i, ps, ps.bemit, ps.o, hr.obj, cont, false, 0u);
+    }
+}
+// The instance for a compact scene: Phong and MIS from a.features, as the render launchers take them
+// (launch_mk_features, launch_megakernel_f64's BVH cases); the mesh, guard and LDS-table bits by `guards`.
+hipError_t launch_diag_vertex_fused(const DevScene& sc, const RenderArgs& a, const DiagVertexArgs& v, int guards,
+                                    bool mesh_nearest, hipStream_t st) {
+    if (v.n <= 0) return hipSuccess;
+    if (!sc.compact) return hipErrorInvalidValue;
+    const bool mesh = (a.features & 1) != 0;
+    if ((guards == 1 && mesh) || (guards == 2 && !mesh) || (mesh_nearest && guards == 1)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((v.n + 255) / 256)), block(256);
+    const int pm = a.features & 6;  // Phong, MIS
+#define RT_DV_CASE(PM, F, COLD)                                                                       \
+    case PM: hipLaunchKernelGGL((k_diag_vertex_fused<(F) | (PM), COLD>), grid, block, 0, st, sc, a, v); break;
+#define RT_DV_SWITCH(F, COLD)                                                                         \
+    switch (pm) { RT_DV_CASE(0, F, COLD) RT_DV_CASE(2, F, COLD) RT_DV_CASE(4, F, COLD) RT_DV_CASE(6, F, COLD) }
+    const int bvh = mesh_nearest ? 16 : 0;
+    if (guards == 0) {  // k_trace_f64's choice of C for a compact scene: the mesh code compiled in
+        if (bvh) RT_DV_SWITCH(25, false) else RT_DV_SWITCH(9, false)
+    } else if (guards == 1) {
+        RT_DV_SWITCH(8, false)
+    } else if (guards == 2) {
+        if (bvh) RT_DV_SWITCH(25 | kCfgGuards1, false) else RT_DV_SWITCH(9 | kCfgGuards1, false)
+    } else if (!mesh) {  // fused_body's C: F | kCfgLdsObj for a compact scene, | kCfgGuards1 with meshes
+        RT_DV_SWITCH(8 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0), RT_OPT_COLD != 0)
+    } else if (bvh) {
+        RT_DV_SWITCH(25 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgGuards1, RT_OPT_COLD != 0)
+    } else {
+        RT_DV_SWITCH(9 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgGuards1, RT_OPT_COLD != 0)
+    }
+#undef RT_DV_SWITCH
+#undef RT_DV_CASE
+    return hipGetLastError();
+}
+
+// rt_diag_sincos: path_f64.h sincos_2pi per lane.
+__global__ __launch_bounds__(256) void k_diag_sincos(long n, const double* __restrict__ x, double* __restrict__ s,
+                                                     double* __restrict__ c) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double sv, cv;
+    sincos_2pi(x[i], &sv, &cv);
+    s[i] = sv;
+    c[i] = cv;
+}
+hipError_t launch_diag_sincos(long n, const double* x, double* s, double* c, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_diag_sincos, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, x, s, c);
+    return hipGetLastError();
+}
+
 thread_local TailPlan t_tail_plan;
 
 // One launch of the fused body. A frame (L = false) plans its split tail and sums it afterwards; a pixel list

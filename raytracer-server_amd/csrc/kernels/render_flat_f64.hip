@@ -1049,6 +1049,109 @@ hipError_t launch_diag_flat(const DevScene& sc, const DiagArgs& a, bool visible,
     return hipGetLastError();
 }
 
+// rt_diag_vertex, the query pool's deferred-shadow form: the split trace of k_diag_flat (analytic part, near mask,
+// flat_query per near mesh, merged in gen order), then shade_vertex as fpool_body calls it: C = Cfg<F | kCfgLdsObj>
+// with the pool's nospec bit, Cold = RegCold for a nospec instance and LdsCold on a [6][256] column otherwise, and
+// (RT_FPOOL_SINK) LdsQuerySink writing a pending shadow ray into this lane's query columns, origin [3][256] and
+// direction + distance [4][256]. The shadow ray is read back from those columns, as stage 1 of the pool reads it,
+// and resolved with flat_query per mesh of defer.meshes; defer.c is added iff no mesh occludes.
+template <int F>
+__global__ __launch_bounds__(kBlk) void k_diag_vertex_flat(DevScene sc, RenderArgs a, DiagVertexArgs v) {
+    using C = Cfg<F | kCfgLdsObj>;
+    static_assert(kBlk == 256, "LdsCold's columns have a stride of 256");
+    lds_objects_fill(sc);
+    __shared__ double s_qo[3 * kBlk], s_qds[4 * kBlk];
+    [[maybe_unused]] __shared__ double s_cold[6 * kBlk];
+    using Cold = std::conditional_t<C::nospec, RegCold, LdsCold>;
+    const int tid = threadIdx.x;
+    const long i = (long)blockIdx.x * blockDim.x + tid;
+    if (i >= v.n) return;
+    PathState ps = diag_vertex_load(v, i);
+    Cold cold{};
+    if constexpr (!C::nospec) {
+        cold = LdsCold{(LdsD*)s_cold + tid};
+        cold.set_o(ps, ps.o);
+        cold.set_bemit(ps, ps.bemit);
+    }
+    const RayInv inv = make_inv(ps.ray.d);
+    HitRec h = trace_analytic<C>(sc, ps.ray, inv);
+    const uint32_t near = mesh_near_mask<C>(sc, ps.ray, inv, h.obj >= 0 ? h.t : INFINITY);
+    double qt[kFlatMeshes];
+    int qp[kFlatMeshes];
+#pragma unroll
+    for (int m = 0; m < kFlatMeshes; ++m) {
+        qt[m] = 0.0;
+        qp[m] = -1;
+        if (m < sc.n_meshes && ((near >> m) & 1u)) {
+            double t = 0.0;
+            int prim = -1;
+            const bool hit = flat_query(sc, m, ps.ray, &t, &prim);
+            qt[m] = t;
+            qp[m] = hit ? prim : -1;
+        }
+    }
+    CTab* T = tables(sc);
+    for (int g = 0; g < T->n_gen; ++g) {
+        const int mm = T->gen_mesh[g];
+#pragma unroll
+        for (int m = 0; m < kFlatMeshes; ++m)
+            if (mm == m && ((near >> m) & 1u) && qp[m] >= 0) consider(h, qt[m], T->gen_idx[g], qp[m]);
+    }
+    ShadowDefer df;
+    df.pending = false;
+    df.meshes = 0u;
+    df.c = v3(0.0, 0.0, 0.0);
+#if RT_FPOOL_SINK
+    const LdsQuerySink qsink{(LdsD*)s_qo + tid, (LdsD*)s_qds + tid, kBlk};
+    const bool cont = shade_vertex<C, Cold, LdsQuerySink>(sc, a, ps, h, &df, cold, qsink);
+#else
+    const bool cont = shade_vertex<C, Cold>(sc, a, ps, h, &df, cold);
+#endif
+    const uint32_t smask = df.pending ? df.meshes : 0u;
+    bool occluded = false;
+#pragma unroll
+    for (int m = 0; m < kFlatMeshes; ++m) {
+        if (m < sc.n_meshes && ((smask >> m) & 1u)) {
+#if RT_FPOOL_SINK
+            const LdsD* qo = (const LdsD*)s_qo;
+            const LdsD* q = (const LdsD*)s_qds;
+            const Ray sr{v3(qo[tid], qo[kBlk + tid], qo[2 * kBlk + tid]), v3(q[tid], q[kBlk + tid], q[2 * kBlk + tid])};
+            const double dist = q[3 * kBlk + tid];
+#else
+            const Ray sr{df.o, df.d};
+            const double dist = df.dist;
+#endif
+            double t = 0.0;
+            int prim = -1;
+            const bool hit = flat_query(sc, m, sr, &t, &prim);
+            occluded |= hit && !(t + 0.001 >= dist);
+        }
+    }
+    if (df.pending && !occluded) ps.L = ps.L + df.c;
+    diag_vertex_store(v, i, ps, cold.bemit(ps), cold.o(ps), h.obj, cont, df.pending, smask);
+}
+hipError_t launch_diag_vertex_flat(const DevScene& sc, const RenderArgs& a, const DiagVertexArgs& v, hipStream_t st) {
+    if (v.n <= 0) return hipSuccess;
+    if (!a.all_flat) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((v.n + kBlk - 1) / kBlk)), block(kBlk);
+    if (fpool_nospec(a)) {  // launch_fpool_product's instances
+        switch (a.features & 15) {
+            case 9: hipLaunchKernelGGL(k_diag_vertex_flat<9 | 32>, grid, block, 0, st, sc, a, v); break;
+            case 13: hipLaunchKernelGGL(k_diag_vertex_flat<13 | 32>, grid, block, 0, st, sc, a, v); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (a.features & 15) {
+            case 9: hipLaunchKernelGGL(k_diag_vertex_flat<9>, grid, block, 0, st, sc, a, v); break;
+            case 11: hipLaunchKernelGGL(k_diag_vertex_flat<11>, grid, block, 0, st, sc, a, v); break;
+            case 13: hipLaunchKernelGGL(k_diag_vertex_flat<13>, grid, block, 0, st, sc, a, v); break;
+            case 15: hipLaunchKernelGGL(k_diag_vertex_flat<15>, grid, block, 0, st, sc, a, v); break;
+            default: return hipErrorInvalidValue;
+        }
+    }
+    return hipGetLastError();
+}
+
 #define RT_DIAG_TU_FN diag_read_flat
 #include "diag_tu.h"
 

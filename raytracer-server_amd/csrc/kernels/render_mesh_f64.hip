@@ -1344,11 +1344,35 @@ hipError_t launch_render_list_roles_f64(const DevScene& sc, const RenderArgs& a,
     return hipGetLastError();
 }
 
+// The meshes' part of a split query, shared by the diagnostic kernels below: the slot walk of each mesh of `near` in
+// gen order, begun as pool_round begins it (next_mesh_walk_near<C>: no second cull) with an LDS ancestor column,
+// to its end. Closest (vis = false): the hits are merged into h by consider; shadow (vis = true): true as soon as a
+// walk's hit blocks the segment of length dist. C: the calling kernel's Cfg.
+template <class C>
+RT_DEV bool diag_slots_meshes(const DevScene& sc, const Ray& r, const RayInv& inv, bool vis, double dist, uint32_t near,
+                              HitRec& h, LdsAncI32* anc) {
+    bool occluded = false;
+    OctWalk w;
+    int g = -1, mi = -1;
+    while (!occluded) {
+        const double tmax = vis ? dist : (h.obj >= 0 ? h.t : INFINITY);
+        if (!next_mesh_walk_near<C, true>(sc, r, inv, tmax, g, mi, w, near)) break;
+        double t;
+        int prim, st;
+        while ((st = walk_step<true, 256, RT_WALK_HOIST>(sc, sc.meshes[mi], r, inv, w, &t, &prim, anc)) == WALK_RUN) {
+        }
+        if (st == WALK_HIT) {
+            if (vis) occluded = !(t + 0.001 >= dist);  // mutually_visible's ERR_MARGIN
+            else consider(h, t, tables(sc)->gen_idx[g], prim);
+        }
+    }
+    return occluded;
+}
+
 // rt_diag_trace / rt_diag_visible, the roles and walk pools' split of a query (compact scenes with slot tables):
 // the analytic part (trace_analytic / visible_analytic), mesh_near_mask at the analytic hit's t (closest) or
-// |y - x| (shadow), then the slot walk of each near mesh in gen order, begun as pool_round begins it
-// (next_mesh_walk_near: no second cull) with an LDS ancestor column, and merged by consider (closest) or
-// ended by the first blocking hit (shadow). One lane per query, walks run to their end.
+// |y - x| (shadow), then the slot walk of each near mesh in gen order (diag_slots_meshes), merged by consider
+// (closest) or ended by the first blocking hit (shadow). One lane per query, walks run to their end.
 __global__ __launch_bounds__(256) void k_diag_slots(DevScene sc, DiagArgs a, int vis) {
     using C = Cfg<9>;
     __shared__ int32_t s_anc[kSlotAncLevels * 256];
@@ -1372,24 +1396,71 @@ __global__ __launch_bounds__(256) void k_diag_slots(DevScene sc, DiagArgs a, int
     }
     const uint32_t near = mesh_near_mask<C>(sc, r, inv, vis ? dist : (h.obj >= 0 ? h.t : INFINITY));
     bool occluded = !clear;
-    if (clear && near) {
-        OctWalk w;
-        int g = -1, mi = -1;
-        while (!occluded) {
-            const double tmax = vis ? dist : (h.obj >= 0 ? h.t : INFINITY);
-            if (!next_mesh_walk_near<C, true>(sc, r, inv, tmax, g, mi, w, near)) break;
-            double t;
-            int prim, st;
-            while ((st = walk_step<true, 256, RT_WALK_HOIST>(sc, sc.meshes[mi], r, inv, w, &t, &prim, anc)) == WALK_RUN) {
-            }
-            if (st == WALK_HIT) {
-                if (vis) occluded = !(t + 0.001 >= dist);  // mutually_visible's ERR_MARGIN
-                else consider(h, t, tables(sc)->gen_idx[g], prim);
-            }
-        }
-    }
+    if (clear && near) occluded = diag_slots_meshes<C>(sc, r, inv, vis != 0, dist, near, h, anc);
     if (vis) diag_store_vis(a, i, !occluded, near);
     else diag_store_hit(sc, a, i, r, h, near);
+}
+
+// rt_diag_vertex, the deferred-shadow forms of the slot-walk pools: the split trace above, then shade_vertex with a
+// ShadowDefer and C = Cfg<F | kCfgLdsObj>, RegCold, as the pools call it.
+//   kSink = false (RT_DIAG_SPLIT_SLOTS): the walk pool's call, shade_vertex<C>(.., &df): the shadow ray comes back
+//     in the ShadowDefer (o, d, dist, inv).
+//   kSink = true (RT_DIAG_SPLIT_ROLES): the roles pool's call, shade_vertex<C, RegCold, LdsQuerySink>: the ray is
+//     written to the lane's LDS columns (origin [3][256], direction + distance [4][256], as the roles kernel's path
+//     store takes them) and read back from there; the walkers take their own reciprocals of the stored direction.
+// A pending shadow query is resolved as the pools resolve it: the slot walk of each mesh of defer.meshes, occluded
+// iff a hit has !(t + 0.001 >= dist), and defer.c is added iff none occludes.
+template <int F, bool kSink>
+__global__ __launch_bounds__(256) void k_diag_vertex_slots(DevScene sc, RenderArgs a, DiagVertexArgs v) {
+    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0)>;
+    if constexpr (C::ldsobj) lds_objects_fill(sc);
+    __shared__ int32_t s_anc[kSlotAncLevels * 256];
+    LdsAncI32* anc = (LdsAncI32*)s_anc + threadIdx.x;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= v.n) return;
+    PathState ps = diag_vertex_load(v, i);
+    const RayInv inv = make_inv(ps.ray.d);
+    HitRec h = trace_analytic<C>(sc, ps.ray, inv);
+    const uint32_t near = mesh_near_mask<C>(sc, ps.ray, inv, h.obj >= 0 ? h.t : INFINITY);
+    if (near) diag_slots_meshes<C>(sc, ps.ray, inv, false, 0.0, near, h, anc);
+    ShadowDefer df;
+    df.pending = false;
+    df.meshes = 0u;
+    HitRec none{0.0, -1, -1};
+    bool cont;
+    if constexpr (kSink) {
+        __shared__ double s_qo[3 * 256], s_qd[4 * 256];
+        LdsDouble* qo = (LdsDouble*)s_qo + threadIdx.x;
+        LdsDouble* qd = (LdsDouble*)s_qd + threadIdx.x;
+        const LdsQuerySink sink{qo, qd, 256};
+        cont = shade_vertex<C>(sc, a, ps, h, &df, RegCold(), sink);
+        if (df.pending) {
+            const Ray sr{v3(qo[0], qo[256], qo[512]), v3(qd[0], qd[256], qd[512])};
+            if (!diag_slots_meshes<C>(sc, sr, make_inv(sr.d), true, qd[768], df.meshes, none, anc)) ps.L = ps.L + df.c;
+        }
+    } else {
+        cont = shade_vertex<C>(sc, a, ps, h, &df);
+        if (df.pending && !diag_slots_meshes<C>(sc, Ray{df.o, df.d}, df.inv, true, df.dist, df.meshes, none, anc))
+            ps.L = ps.L + df.c;
+    }
+    diag_vertex_store(v, i, ps, ps.bemit, ps.o, h.obj, cont, df.pending, df.pending ? df.meshes : 0u);
+}
+hipError_t launch_diag_vertex_slots(const DevScene& sc, const RenderArgs& a, const DiagVertexArgs& v, bool sink,
+                                    hipStream_t st) {
+    if (v.n <= 0) return hipSuccess;
+    if (!sc.node_slot) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((v.n + 255) / 256)), block(256);
+#define RT_DVS_CASE(F)                                                                              \
+    case F:                                                                                         \
+        if (sink) hipLaunchKernelGGL((k_diag_vertex_slots<F, true>), grid, block, 0, st, sc, a, v); \
+        else hipLaunchKernelGGL((k_diag_vertex_slots<F, false>), grid, block, 0, st, sc, a, v);     \
+        break;
+    switch (a.features & 31) {  // launch_megakernel_mesh_f64's octree cases
+        RT_DVS_CASE(9) RT_DVS_CASE(11) RT_DVS_CASE(13) RT_DVS_CASE(15)
+        default: return hipErrorInvalidValue;
+    }
+#undef RT_DVS_CASE
+    return hipGetLastError();
 }
 hipError_t launch_diag_slots(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st) {
     if (a.n <= 0) return hipSuccess;

@@ -622,10 +622,34 @@ int wavefront_render_f64(const DevScene& sc, const RenderArgs& a_in, Workspace& 
     return RT_OK;
 }
 
+// The meshes' part of a candidate's query, shared by the diagnostic kernels below: the node_kids walk of every
+// mesh object in gen order, as ClosestQuery / ShadowQuery walk them (walk_begin<false> with its own f64 cull at the
+// closest t so far or |y - x|, walk_step<false> to the walk's end). Closest (vis = false): the hits are merged into
+// h by consider; shadow (vis = true): true as soon as a hit blocks the segment of length dist.
+RT_DEV bool diag_kids_meshes(const DevScene& sc, const Ray& r, const RayInv& inv, bool vis, double dist, HitRec& h) {
+    bool occluded = false;
+    OctWalk w;
+    for (int g = 0; g < tables(sc)->n_gen && !occluded; ++g) {
+        const int idx = tables(sc)->gen_idx[g];
+        const DevObject& o = sc.objects[idx];
+        if (o.geom != GEOM_MESH) continue;
+        const DevMesh& m = sc.meshes[o.mesh];
+        if (!walk_begin<false>(sc, m, r, inv, vis ? dist : (h.obj >= 0 ? h.t : INFINITY), w)) continue;
+        double t;
+        int prim, st;
+        while ((st = walk_step<false>(sc, m, r, inv, w, &t, &prim)) == WALK_RUN) {
+        }
+        if (st == WALK_HIT) {
+            if (vis) occluded = !(t + 0.001 >= dist);  // mesh_occludes / mutually_visible's ERR_MARGIN
+            else consider(h, t, idx, prim);
+        }
+    }
+    return occluded;
+}
+
 // rt_diag_trace / rt_diag_visible, the wavefront's split of a query (compact scenes): k_wf_extend's analytic
 // part and mesh_candidate (closest), shade_vertex's visible_analytic and near mask (shadow); a candidate then
-// walks every mesh object in gen order as ClosestQuery / ShadowQuery do: walk_begin<false> with its own f64
-// cull at the closest t so far (closest) or |y - x| (shadow), walk_step<false> to the walk's end.
+// walks every mesh object in gen order (diag_kids_meshes).
 __global__ __launch_bounds__(kBlock) void k_diag_kids(DevScene sc, DiagArgs a, int vis) {
     using C = Cfg<9>;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -647,26 +671,46 @@ __global__ __launch_bounds__(kBlock) void k_diag_kids(DevScene sc, DiagArgs a, i
     }
     const uint32_t near = mesh_near_mask<C>(sc, r, inv, vis ? dist : (h.obj >= 0 ? h.t : INFINITY));
     bool occluded = !clear;
-    if (clear && near) {
-        OctWalk w;
-        for (int g = 0; g < tables(sc)->n_gen && !occluded; ++g) {
-            const int idx = tables(sc)->gen_idx[g];
-            const DevObject& o = sc.objects[idx];
-            if (o.geom != GEOM_MESH) continue;
-            const DevMesh& m = sc.meshes[o.mesh];
-            if (!walk_begin<false>(sc, m, r, inv, vis ? dist : (h.obj >= 0 ? h.t : INFINITY), w)) continue;
-            double t;
-            int prim, st;
-            while ((st = walk_step<false>(sc, m, r, inv, w, &t, &prim)) == WALK_RUN) {
-            }
-            if (st == WALK_HIT) {
-                if (vis) occluded = !(t + 0.001 >= dist);  // mesh_occludes / mutually_visible's ERR_MARGIN
-                else consider(h, t, idx, prim);
-            }
-        }
-    }
+    if (clear && near) occluded = diag_kids_meshes(sc, r, inv, vis != 0, dist, h);
     if (vis) diag_store_vis(a, i, !occluded, near);
     else diag_store_hit(sc, a, i, r, h, near);
+}
+
+// rt_diag_vertex, the wavefront's deferred-shadow form: the split trace above (k_wf_extend, k_wf_mesh_closest),
+// then shade_vertex<Cfg<F>> with a ShadowDefer as k_wf_shade calls it (RegCold, the ray returned in the
+// ShadowDefer). A pending shadow query is resolved as k_wf_shadow_mesh resolves it: the node_kids walk of every
+// mesh with the query's own reciprocals, and defer.c is added iff no mesh occludes.
+template <int F>
+__global__ __launch_bounds__(kBlock) void k_diag_vertex_kids(DevScene sc, RenderArgs a, DiagVertexArgs v) {
+    using C = Cfg<F>;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= v.n) return;
+    PathState ps = diag_vertex_load(v, i);
+    const RayInv inv = make_inv(ps.ray.d);
+    HitRec h = trace_analytic<C>(sc, ps.ray, inv);
+    if (mesh_candidate<C>(sc, ps.ray, inv, h.obj >= 0 ? h.t : INFINITY)) diag_kids_meshes(sc, ps.ray, inv, false, 0.0, h);
+    ShadowDefer sd;
+    sd.pending = false;
+    sd.meshes = 0u;
+    const bool cont = shade_vertex<C>(sc, a, ps, h, &sd);
+    if (sd.pending) {
+        HitRec none{0.0, -1, -1};
+        const Ray sr{sd.o, sd.d};
+        if (!diag_kids_meshes(sc, sr, make_inv(sr.d), true, sd.dist, none)) ps.L = ps.L + sd.c;
+    }
+    diag_vertex_store(v, i, ps, ps.bemit, ps.o, h.obj, cont, sd.pending, sd.pending ? sd.meshes : 0u);
+}
+hipError_t launch_diag_vertex_kids(const DevScene& sc, const RenderArgs& a, const DiagVertexArgs& v, hipStream_t st) {
+    if (v.n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((v.n + kBlock - 1) / kBlock)), block(kBlock);
+    switch (a.features & 15) {  // launch_bounce's cases with deferred mesh queries (mesh and compact)
+        case 9: hipLaunchKernelGGL(k_diag_vertex_kids<9>, grid, block, 0, st, sc, a, v); break;
+        case 11: hipLaunchKernelGGL(k_diag_vertex_kids<11>, grid, block, 0, st, sc, a, v); break;
+        case 13: hipLaunchKernelGGL(k_diag_vertex_kids<13>, grid, block, 0, st, sc, a, v); break;
+        case 15: hipLaunchKernelGGL(k_diag_vertex_kids<15>, grid, block, 0, st, sc, a, v); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 hipError_t launch_diag_kids(const DevScene& sc, const DiagArgs& a, bool visible, hipStream_t st) {
     if (a.n <= 0) return hipSuccess;

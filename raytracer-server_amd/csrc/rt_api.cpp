@@ -2743,4 +2743,105 @@ int rt_diag_visible(const rt_scene* scene, int32_t device, int32_t form, uint32_
     return diag_run("rt_diag_visible", scene, device, form, flags, true, a, x, y, &a.a, &a.b, outs, 2);
 }
 
+int rt_diag_vertex(const rt_scene* scene, int32_t device, int32_t form, uint32_t flags, int64_t n, const double* st,
+                   const uint64_t* rng, const int32_t* dk, double* st_out, uint64_t* rng_out, int32_t* dk_out,
+                   int32_t* info) {
+    const char* who = "rt_diag_vertex";
+    if (!scene || !st || !rng || !dk || !st_out || !rng_out || !dk_out || !info)
+        return fail(RT_E_INVAL, std::string(who) + ": null argument");
+    if (n < 0) return fail(RT_E_INVAL, std::string(who) + ": n must be >= 0");
+    if (form < RT_DIAG_FUSED || form > RT_DIAG_SPLIT_ROLES) return fail(RT_E_INVAL, std::string(who) + ": unknown form");
+    if (flags & ~(uint32_t)(RT_FLAG_MIS | RT_FLAG_MESH_NEAREST)) return fail(RT_E_INVAL, std::string(who) + ": unknown flag");
+    const bool split = (form >= RT_DIAG_SPLIT_SLOTS && form <= RT_DIAG_SPLIT_FLAT) || form == RT_DIAG_SPLIT_ROLES;
+    if (split) {  // what rt_diag_trace asks of the scene for these forms (the roles form: what the slot form asks);
+                  // their kernels walk octrees only
+        const int rc = check_diag(who, scene, form == RT_DIAG_SPLIT_ROLES ? RT_DIAG_SPLIT_SLOTS : form,
+                                  flags & RT_FLAG_MESH_NEAREST, n, true);
+        if (rc != RT_OK) return rc;
+    }
+    int32_t compact = 0;
+    {
+        rt::CompactTab tab;
+        fill_compact(scene->packed, &tab, &compact);
+    }
+    const bool meshes = !scene->host.meshes.empty();
+    if (!compact) return fail(RT_E_INVAL, std::string(who) + ": needs a compact scene");
+    if (form == RT_DIAG_FUSED_G0 && (meshes || (flags & RT_FLAG_MESH_NEAREST)))
+        return fail(RT_E_INVAL, std::string(who) + ": the mesh-free fused form needs a scene without meshes and no mesh flag");
+    if (form == RT_DIAG_FUSED_G1 && !meshes)
+        return fail(RT_E_INVAL, std::string(who) + ": this form needs a scene with meshes");
+    if (n == 0) return RT_OK;
+    int rc = need_device(who, device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    rt::DevScene ds;
+    if ((rc = upload(const_cast<rt_scene*>(scene), device, &ds)) != RT_OK) return rc;
+    rt_render_params p{};
+    p.width = p.height = p.tile_w = p.tile_h = 4;
+    p.spp = 4;
+    p.flags = flags;
+    const rt::RenderArgs a = make_render_args(scene, &p, ds.compact);  // the Cfg bits of a render with these flags
+    const size_t rows = (size_t)n;
+    const size_t b_st = rows * 19 * sizeof(double), b_rng = rows * 2 * sizeof(uint64_t), b_dk = rows * 2 * sizeof(int32_t),
+                 b_info = rows * 4 * sizeof(int32_t);
+    DeviceBlock buf;
+    const size_t at_st = buf.part(b_st), at_rng = buf.part(b_rng), at_dk = buf.part(b_dk), at_sto = buf.part(b_st),
+                 at_rngo = buf.part(b_rng), at_dko = buf.part(b_dk), at_info = buf.part(b_info);
+    hipError_t e = buf.alloc();
+    if (e != hipSuccess) return oom_or_hip(e, std::string(who) + " buffers");
+    rt::DiagVertexArgs v{};
+    v.n = (long)n;
+    v.st = buf.at<const double>(at_st);
+    v.rng = buf.at<const uint64_t>(at_rng);
+    v.dk = buf.at<const int32_t>(at_dk);
+    v.st_out = buf.at<double>(at_sto);
+    v.rng_out = buf.at<uint64_t>(at_rngo);
+    v.dk_out = buf.at<int32_t>(at_dko);
+    v.info = buf.at<int32_t>(at_info);
+    e = hipMemcpy(buf.at<void>(at_st), st, b_st, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf.at<void>(at_rng), rng, b_rng, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf.at<void>(at_dk), dk, b_dk, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(buf.at<void>(at_sto), 0, buf.bytes - at_sto);
+    if (e == hipSuccess) {
+        if (form == RT_DIAG_SPLIT_SLOTS) e = rt::launch_diag_vertex_slots(ds, a, v, false, nullptr);
+        else if (form == RT_DIAG_SPLIT_ROLES) e = rt::launch_diag_vertex_slots(ds, a, v, true, nullptr);
+        else if (form == RT_DIAG_SPLIT_KIDS) e = rt::launch_diag_vertex_kids(ds, a, v, nullptr);
+        else if (form == RT_DIAG_SPLIT_FLAT) e = rt::launch_diag_vertex_flat(ds, a, v, nullptr);
+        else
+            e = rt::launch_diag_vertex_fused(ds, a, v, form == RT_DIAG_FUSED_G0 ? 1 : form == RT_DIAG_FUSED_G1 ? 2
+                                                       : form == RT_DIAG_FUSED_LDS ? 3 : 0,
+                                             (flags & RT_FLAG_MESH_NEAREST) != 0 && meshes, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(st_out, v.st_out, b_st, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(rng_out, v.rng_out, b_rng, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(dk_out, v.dk_out, b_dk, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(info, v.info, b_info, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_diag_sincos(int32_t device, int64_t n, const double* x, double* s, double* c) {
+    const char* who = "rt_diag_sincos";
+    if (!x || !s || !c) return fail(RT_E_INVAL, std::string(who) + ": null argument");
+    if (n < 0) return fail(RT_E_INVAL, std::string(who) + ": n must be >= 0");
+    if (n == 0) return RT_OK;
+    int rc = need_device(who, device);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t bytes = (size_t)n * sizeof(double);
+    DeviceBlock buf;
+    const size_t at_x = buf.part(bytes), at_s = buf.part(bytes), at_c = buf.part(bytes);
+    hipError_t e = buf.alloc();
+    if (e != hipSuccess) return oom_or_hip(e, std::string(who) + " buffers");
+    e = hipMemcpy(buf.at<void>(at_x), x, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = rt::launch_diag_sincos((long)n, buf.at<const double>(at_x), buf.at<double>(at_s), buf.at<double>(at_c), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(s, buf.at<void>(at_s), bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(c, buf.at<void>(at_c), bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return RT_OK;
+}
+
 }  // extern "C"

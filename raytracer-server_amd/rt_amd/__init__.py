@@ -36,6 +36,8 @@ FLAG_FP32 = 1 << 2
 FLAG_MESH_NEAREST = 1 << 3  # Mesh::intersect without the octree (geometry.rs:886-903), BVH on the device
 # query forms of Scene.diag_trace / diag_visible (include/rt_diag.h RT_DIAG_*)
 DIAG_FUSED, DIAG_FUSED_G0, DIAG_SPLIT_SLOTS, DIAG_SPLIT_KIDS, DIAG_SPLIT_FLAT, DIAG_FUSED_G1 = range(6)
+DIAG_FUSED_LDS = 6  # Scene.diag_vertex only: the fused megakernel's own instantiation (LDS object table, LdsCold)
+DIAG_SPLIT_ROLES = 7  # Scene.diag_vertex only: the roles pool's instantiation (LdsQuerySink, slot walks)
 # kernel families of a pixel-list render (include/rt_ffi.h RT_LIST_*): the automatic choice, k_render_list_f64, the
 # flat-octree query pool, the role-split pool
 LIST_AUTO, LIST_FUSED, LIST_FPOOL, LIST_ROLES = range(4)
@@ -188,6 +190,11 @@ def _load():
         L.rt_diag_trace.argtypes = [vp, I, I, ctypes.c_uint32, ctypes.c_int64, P(D), P(D), P(D), P(I), P(I), P(D), P(D)]
         L.rt_diag_visible.argtypes = [vp, I, I, ctypes.c_uint32, ctypes.c_int64, P(D), P(D), P(ctypes.c_uint8),
                                       P(ctypes.c_uint32)]
+    if hasattr(L, "rt_diag_vertex"):
+        D, U64 = ctypes.c_double, ctypes.c_uint64
+        L.rt_diag_vertex.argtypes = [vp, I, I, ctypes.c_uint32, ctypes.c_int64, P(D), P(U64), P(I), P(D), P(U64), P(I),
+                                     P(I)]
+        L.rt_diag_sincos.argtypes = [I, ctypes.c_int64, P(D), P(D), P(D)]
     return L
 
 
@@ -365,6 +372,23 @@ class Scene:
         _check(lib.rt_diag_visible(self._h, device, form, FLAG_MESH_NEAREST if mesh_nearest else 0, n, _ptr(x, D),
                                    _ptr(y, D), _ptr(vis, ctypes.c_uint8), _ptr(near, ctypes.c_uint32)))
         return vis.astype(bool), near
+
+    def diag_vertex(self, st, rng, dk, form=0, mis=False, mesh_nearest=False, device=0):
+        """One path vertex per row through the integrator of one kernel family (rt_diag.h rt_diag_vertex, form =
+        DIAG_*): st (n, 19) = ray origin, ray direction, beta, L, bemit, o, pdf_prev; rng (n, 2) uint64; dk (n, 2)
+        int32 = depth, kind. Returns dict(st, rng, dk: the rows after the vertex; info (n, 4) int32 = hit object,
+        continue flag, deferred shadow pending, its mesh mask)."""
+        st = np.ascontiguousarray(st, dtype=np.float64).reshape(-1, 19)
+        rng = np.ascontiguousarray(rng, dtype=np.uint64).reshape(-1, 2)
+        dk = np.ascontiguousarray(dk, dtype=np.int32).reshape(-1, 2)
+        n = st.shape[0]
+        so, ro, do = np.zeros_like(st), np.zeros_like(rng), np.zeros_like(dk)
+        info = np.zeros((n, 4), dtype=np.int32)
+        D, U64, I = ctypes.c_double, ctypes.c_uint64, ctypes.c_int32
+        flags = (FLAG_MIS if mis else 0) | (FLAG_MESH_NEAREST if mesh_nearest else 0)
+        _check(lib.rt_diag_vertex(self._h, device, form, flags, n, _ptr(st, D), _ptr(rng, U64), _ptr(dk, I),
+                                  _ptr(so, D), _ptr(ro, U64), _ptr(do, I), _ptr(info, I)))
+        return dict(st=so, rng=ro, dk=do, info=info)
 
 
 def make_params(width, height, spp, seed=0x5EED, tile=None, flags=0, device=0, row_step=1):
@@ -941,6 +965,16 @@ def selftest_tables(ptrs):
     out = (ctypes.c_ulonglong * (6 * n))()
     _check(lib.rt_selftest_tables(inp, n, out))
     return [tuple(int(out[6 * i + k]) for k in range(6)) for i in range(n)]
+
+
+def diag_sincos(x, device=0):
+    """The device sincos_2pi (csrc/device/path_f64.h) of an array of doubles in [0, 2 pi] (rt_diag.h
+    rt_diag_sincos): (sin, cos)."""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    s, c = np.zeros_like(x), np.zeros_like(x)
+    D = ctypes.c_double
+    _check(lib.rt_diag_sincos(device, x.shape[0], _ptr(x, D), _ptr(s, D), _ptr(c, D)))
+    return s, c
 
 
 def debug_qcheck():

@@ -64,6 +64,19 @@ def lib():
         L.orc_render.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int,
                                  ctypes.c_int, _U8, _D, _I64]
+        _U64 = ctypes.POINTER(ctypes.c_uint64)
+        L.orc_stream.restype = None
+        L.orc_stream.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _D, _U64]
+        L.orc_sincos.restype = None
+        L.orc_sincos.argtypes = [ctypes.c_int64, _D, _D, _D]
+        L.orc_light_areas.restype = ctypes.c_int64
+        L.orc_light_areas.argtypes = [ctypes.c_void_p, _D]
+        L.orc_camera_states.restype = None
+        L.orc_camera_states.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64,
+                                        _I32, _I32, _I32, _I32, _D, _U64, _I32]
+        L.orc_vertex.restype = None
+        L.orc_vertex.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _I32, _D, _U64, _I32,
+                                 _D, _U64, _I32, _I32, _D]
         _lib = L
     return _lib
 
@@ -206,6 +219,41 @@ class OracleScene:
         lib().orc_visible(self.h, x.shape[0], _dp(x), _dp(y), out.ctypes.data_as(_U8))
         return out.astype(bool)
 
+    def light_areas(self):
+        """The mesh light's triangle_selector weights (geometry.rs:588), empty for a sphere light."""
+        n = lib().orc_light_areas(self.h, None)
+        a = np.zeros(max(1, n))
+        lib().orc_light_areas(self.h, _dp(a))
+        return a[:n]
+
+    def camera_states(self, width, height, seed, col, row, sub, smp):
+        """The path states on arrival at the first vertex of the given camera samples (orc_camera_states):
+        st (n, 19), rng (n, 2) uint64, dk (n, 2) int32 — the rows of vertex()."""
+        c, r, s, m = (np.ascontiguousarray(v, dtype=np.int32) for v in (col, row, sub, smp))
+        n = c.shape[0]
+        st, rng, dk = np.zeros((n, 19)), np.zeros((n, 2), dtype=np.uint64), np.zeros((n, 2), dtype=np.int32)
+        P = lambda a: a.ctypes.data_as(_I32)
+        lib().orc_camera_states(self.h, width, height, seed, n, P(c), P(r), P(s), P(m), _dp(st),
+                                rng.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), P(dk))
+        return st, rng, dk
+
+    def vertex(self, st, rng, dk, mis=False, variant=1, nudge=(0, 0, 0, 0)):
+        """One path vertex per row (orc_vertex): the state each path carries on, in the input's layout, plus
+        info (n, 6) int32 = hit object, continue, survived, lobe, NEE visibility, light triangle and
+        aux (n, 13) = hit t, vertex x, light sample y, normal at x, normal at y."""
+        st = np.ascontiguousarray(st, dtype=np.float64).reshape(-1, 19)
+        rng = np.ascontiguousarray(rng, dtype=np.uint64).reshape(-1, 2)
+        dk = np.ascontiguousarray(dk, dtype=np.int32).reshape(-1, 2)
+        n = st.shape[0]
+        so, ro, do = np.zeros_like(st), np.zeros_like(rng), np.zeros_like(dk)
+        info, aux = np.zeros((n, 6), dtype=np.int32), np.zeros((n, 13))
+        ng = np.array(nudge, dtype=np.int32)
+        U = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        P = lambda a: a.ctypes.data_as(_I32)
+        lib().orc_vertex(self.h, n, int(mis), int(variant), P(ng), _dp(st), U(rng), P(dk), _dp(so), U(ro), P(do),
+                         P(info), _dp(aux))
+        return dict(st=so, rng=ro, dk=do, info=info, aux=aux)
+
     def render(self, width, height, spp, seed, tile=None, mis=False, threads=None, want_sub=True):
         x0, y0, tw, th = tile if tile is not None else (0, 0, width, height)
         rgb = np.zeros((th, tw, 3), dtype=np.uint8)
@@ -231,6 +279,22 @@ def philox(ctr, key):
     P = lambda a: a.ctypes.data_as(_U32)
     lib().orc_philox(P(c), P(k), P(o))
     return [int(x) for x in o]
+
+
+def stream(s0, s1, n=8):
+    """The first n uniforms of the xoroshiro128++ stream with raw state (s0, s1), and the state after them."""
+    out = np.zeros(n)
+    after = np.zeros(2, dtype=np.uint64)
+    lib().orc_stream(int(s0), int(s1), n, _dp(out), after.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+    return out, (int(after[0]), int(after[1]))
+
+
+def sincos(x):
+    """glibc's sin and cos of an array of doubles."""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    s, c = np.zeros_like(x), np.zeros_like(x)
+    lib().orc_sincos(x.shape[0], _dp(x), _dp(s), _dp(c))
+    return s, c
 
 
 def draws(seed, pixel, sample, sub, n=8):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import scene_path
+from extra_scenes import QUIRK_SCENE
 
 pytestmark = pytest.mark.gpu
 
@@ -452,33 +453,6 @@ def test_deep_mesh_mis_and_phong_parity(phong, rt, oracle, tmp_path):
 
 
 # ---------------------------------------------------------------- reference quirks off the 3 scenes
-QUIRK_SCENE = """
-[camera]
-pos = [0.0, 6.0, 60.0]
-dir = [0.0, -0.1, -1.0]
-[[objects]]
-emitted = [12.0, 12.0, 12.0]
-brdf = { type = "diffuse", kd = [0.0, 0.0, 0.0] }
-geometry = { type = "cube", pos = [6.0, 14.0, -4.0], size = 4.0 }
-transforms = [ { rotate_y = 0.3 } ]
-[[objects]]
-brdf = { type = "phong", kd = 0.5, ks = 0.3, power = 8, color_d = [0.7, 0.6, 0.5], color_s = [1.0, 1.0, 1.0] }
-geometry = { type = "plane", pos = [0.0, -5.0, 0.0], n = [0.0, 1.0, 0.0] }
-[[objects]]
-brdf = { type = "diffuse", kd = [0.6, 0.6, 0.75] }
-geometry = { type = "plane", pos = [0.0, 0.0, -30.0], n = [0.0, 0.0, 1.0] }
-[[objects]]
-brdf = { type = "phong", kd = 0.2, ks = 0.7, power = 24, color_d = [0.9, 0.3, 0.3], color_s = [1.0, 1.0, 1.0] }
-geometry = { type = "sphere", pos = [-8.0, 0.0, 2.0], r = 5.0 }
-[[objects]]
-brdf = { type = "specular", ks = [0.95, 0.95, 0.95] }
-geometry = { type = "sphere", pos = [9.0, -1.0, 6.0], r = 4.0 }
-[[objects]]
-brdf = { type = "diffuse", kd = [0.8, 0.8, 0.8] }
-geometry = { type = "prism", pos = [-2.0, -5.0, -12.0], size = [6.0, 9.0, 5.0] }
-"""
-
-
 def test_phong_and_mesh_light_parity(rt, oracle, tmp_path):
     """Phong BRDFs with the reference's unrotated lobes (scene.rs:56-98) and a
     triangle-mesh emitter (the first emitting object is the light, scene.rs:129-137) sampled with
