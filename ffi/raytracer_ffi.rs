@@ -59,6 +59,8 @@ pub const RT_LIST_FUSED: i32 = 1;
 pub const RT_LIST_FPOOL: i32 = 2;
 /// The role-split pool's list instance.
 pub const RT_LIST_ROLES: i32 = 3;
+/// The most passes per list entry of a batched render (`rt_render_pixel_passes`), and so the most seeds.
+pub const RT_PASSES_MAX: i32 = 16;
 
 pub const RT_BRDF_DIFFUSE: i32 = 0;
 pub const RT_BRDF_SPECULAR: i32 = 1;
@@ -328,6 +330,45 @@ extern "C" {
     pub fn rt_accum_fill(
         accum: *mut c_void, scene: *const RtScene, params: *const RtRenderParams, seed2: u64, period: i32, phase: i32,
         cancel: *const i32, stats: *mut RtRenderStats, fill_out: *mut i64 /* [2] */,
+    ) -> c_int;
+
+    /// Batched passes: `rt_render_pixels` with `counts[e]` passes (1 ..= `n_seeds` <= `RT_PASSES_MAX`)
+    /// of pixel `pixels[e]` in one launch, pass `i` drawing from `seeds[i]`; the outputs are indexed by unit-group
+    /// `off[e] + i` (`off`: the exclusive prefix sum of `counts`), each bit for bit `rt_render_pixels`' for that seed.
+    pub fn rt_render_pixel_passes(
+        scene: *const RtScene, params: *const RtRenderParams, pixels: *const u32, counts: *const u8, n_pixels: i64,
+        seeds: *const u64, n_seeds: i32, rgb_out: *mut u8, sub_out: *mut f64, cancel: *const i32,
+        stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// The same with device lists and outputs; `units` is the sum of the counts; `seeds` stay on the host; waits.
+    pub fn rt_render_pixel_passes_device(
+        scene: *const RtScene, params: *const RtRenderParams, d_pixels: *const c_void, d_counts: *const c_void,
+        n_pixels: i64, units: i64, seeds: *const u64, n_seeds: i32, d_rgb: *mut c_void, d_sub: *mut c_void,
+        stream: *mut c_void, stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// `rt_accum_select` plus a pass count per listed pixel (`n` samples per subpixel per pass, `gain` in (0, 1],
+    /// `max_passes` in 1 ..= `RT_PASSES_MAX`), capped to a frame's worth of units in all.
+    pub fn rt_accum_plan(
+        accum: *mut c_void, abs_tol: f32, rel_tol: f32, max_n: i32, n: i32, gain: f32, max_passes: i32,
+        pixels_out: *mut u32, counts_out: *mut u8, cap: i64, n_out: *mut i64, units_out: *mut i64,
+        passes_out: *mut i64,
+    ) -> c_int;
+    pub fn rt_accum_plan_device(
+        accum: *mut c_void, abs_tol: f32, rel_tol: f32, max_n: i32, n: i32, gain: f32, max_passes: i32,
+        d_pixels: *mut c_void, d_counts: *mut c_void, cap: i64, n_out: *mut i64, units_out: *mut i64,
+        passes_out: *mut i64, stream: *mut c_void,
+    ) -> c_int;
+    /// Renders the listed pixels' passes and merges each entry's units in pass order: the bits of `counts[e]`
+    /// successive sparse merges. `RT_CANCELLED` merges nothing.
+    pub fn rt_accum_add_passes(
+        accum: *mut c_void, scene: *const RtScene, params: *const RtRenderParams, seeds: *const u64, n_seeds: i32,
+        pixels: *const u32, counts: *const u8, n_pixels: i64, cancel: *const i32, stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// Plan, expand, render and merge with the lists on the device; `out` (nullable) = pixels, units, passes used.
+    pub fn rt_accum_refine(
+        accum: *mut c_void, scene: *const RtScene, params: *const RtRenderParams, abs_tol: f32, rel_tol: f32,
+        max_n: i32, gain: f32, seeds: *const u64, n_seeds: i32, cancel: *const i32, stats: *mut RtRenderStats,
+        out: *mut i64 /* [3] */,
     ) -> c_int;
 
     pub fn rt_last_error() -> *const c_char;

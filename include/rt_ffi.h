@@ -452,6 +452,70 @@ int rt_accum_holes_device(void* accum, int32_t period, int32_t phase, void* d_pi
 int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* params, uint64_t seed2, int32_t period,
                   int32_t phase, const volatile int32_t* cancel, rt_render_stats* stats, int64_t fill_out[2]);
 
+/* Batched passes: several error-target passes per pixel in one launch ---------------- */
+/* The most passes one list entry may hold, and so the most seeds a call takes. */
+#define RT_PASSES_MAX 16
+/* rt_render_pixels with a pass count per listed pixel and a seed per pass. Entry e of the list has counts[e] passes,
+ * each count in 1 .. n_seeds, n_seeds in 1 .. RT_PASSES_MAX; unit-group u = off[e] + i is pass i of pixel pixels[e],
+ * off the exclusive prefix sum of counts, and the outputs are indexed by unit-group: sub_out[off[e] + i] (12 f64) is,
+ * bit for bit, rt_render_pixels' sub_out of pixel pixels[e] for the seed seeds[i] and the same spp and flags, and
+ * rgb_out[off[e] + i] its RGB8. params->seed is ignored. params, flags and the list: rt_render_pixels' rules
+ * (RT_FLAG_MIS passes through; RT_FLAG_FP32 and RT_FLAG_MESH_NEAREST are RT_E_INVAL); in addition width * height must
+ * be below 2^28 and the unit total sum(counts) at most width * height (RT_E_INVAL, before any device call). The
+ * fused megakernel's body runs it for every scene (k_render_passes_f64; the pool kernels have no such instance).
+ * n_pixels = 0 returns RT_OK without a launch. cancel and stats as in rt_render;
+ * stats->samples = units * 4 * floor(spp / 4). Every argument check runs without a GPU. */
+int rt_render_pixel_passes(const rt_scene* scene, const rt_render_params* params, const uint32_t* pixels,
+                           const uint8_t* counts, int64_t n_pixels, const uint64_t* seeds /* host */, int32_t n_seeds,
+                           uint8_t* rgb_out /* units * 3, may be NULL */, double* sub_out /* units * 12, may be NULL */,
+                           const volatile int32_t* cancel, rt_render_stats* stats);
+/* The same with device lists and outputs on params->device (d_sub 16-byte aligned; d_rgb, d_sub nullable), enqueued on
+ * `stream`. units: the sum of the counts (rt_accum_plan reports it), n_pixels <= units <= width * height. The list
+ * (strictly ascending ids in range, counts in 1 .. n_seeds that add up to units) is the caller's contract. seeds stay
+ * on the host. The list is expanded on the device into scratch memory that lives for the call, so the call waits for
+ * the render before it returns. */
+int rt_render_pixel_passes_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
+                                  const void* d_counts, int64_t n_pixels, int64_t units, const uint64_t* seeds,
+                                  int32_t n_seeds, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats);
+/* rt_accum_select plus a pass count per listed pixel: how many passes of n samples per subpixel the pixel should get
+ * at once. n >= 1, gain in (0, 1] (the share of the predicted need to hand out), max_passes = C in 1 .. RT_PASSES_MAX,
+ * tolerances and K as rt_accum_select, width * height < 2^28; RT_E_INVAL otherwise, before any device call. For a pixel
+ * that rt_accum_select(abs_tol, rel_tol, max_n) lists, with its g_p, thr and N_p, in f64 without FMA contraction:
+ *   r    = g_p / (thr * thr)                      (IEEE; +inf when thr = 0)
+ *   need = (double)N_p * r - (double)N_p
+ *   x    = ((double)gain * need) / (double)n
+ *   c    = x >= C ? C : max(1, (int)ceil(x))
+ *   max_n > 0: c = min(c, (max_n - N_p + n - 1) / n)           (integers; >= 1 because N_p < max_n)
+ * A launch never holds more than a frame's worth of units: with H[c] the histogram of the counts, C' is the largest
+ * value in 1 .. C with sum_c H[c] min(c, C') <= width * height (C' = 1 always fits), and the final count is
+ * min(c, C'). pixels_out: the ids, ascending, identical to rt_accum_select's list; counts_out: their final counts; at
+ * most cap of each (cap >= 0; both may be NULL when cap = 0). *n_out: the list's full length; *units_out (nullable):
+ * the sum of all final counts; *passes_out (nullable): the largest final count (0 for an empty list). */
+int rt_accum_plan(void* accum, float abs_tol, float rel_tol, int32_t max_n, int32_t n, float gain, int32_t max_passes,
+                  uint32_t* pixels_out, uint8_t* counts_out, int64_t cap, int64_t* n_out, int64_t* units_out,
+                  int64_t* passes_out);
+/* The same into device buffers of the accumulator's device, enqueued on `stream`; the call waits for the plan and then
+ * writes the three totals on the host. */
+int rt_accum_plan_device(void* accum, float abs_tol, float rel_tol, int32_t max_n, int32_t n, float gain,
+                         int32_t max_passes, void* d_pixels, void* d_counts, int64_t cap, int64_t* n_out,
+                         int64_t* units_out, int64_t* passes_out, void* stream);
+/* Renders the listed pixels' passes (rt_render_pixel_passes' rules for params, seeds, the list and the counts; spp >= 4
+ * and params->device the accumulator's) into the staging buffer and merges each entry's counts[e] units in pass order
+ * with n = floor(spp / 4): per element and pass S += (double)n * m; Q += ((double)n * m) * m, then (K_p, N_p) +=
+ * (counts[e], counts[e] * n). The result is, bit for bit, what the loop
+ *   for i in 0 .. max(counts) - 1: rt_accum_add_pixels({pixels[e] : counts[e] > i}, seed = seeds[i])
+ * gives. Needs K >= 2 as every sparse merge does. A cancelled call merges nothing and returns RT_CANCELLED. */
+int rt_accum_add_passes(void* accum, const rt_scene* scene, const rt_render_params* params, const uint64_t* seeds,
+                        int32_t n_seeds, const uint32_t* pixels, const uint8_t* counts, int64_t n_pixels,
+                        const volatile int32_t* cancel, rt_render_stats* stats);
+/* rt_accum_plan(abs_tol, rel_tol, max_n, n = floor(spp / 4), gain, max_passes = n_seeds) followed by
+ * rt_accum_add_passes of the planned lists, which stay on the device (as rt_accum_fill's do): only the histogram and
+ * the totals are read back. out (nullable) = (pixels, units, passes used: the largest final count). An empty plan
+ * launches nothing and returns RT_OK. Every check runs before any device call. */
+int rt_accum_refine(void* accum, const rt_scene* scene, const rt_render_params* params, float abs_tol, float rel_tol,
+                    int32_t max_n, float gain, const uint64_t* seeds, int32_t n_seeds, const volatile int32_t* cancel,
+                    rt_render_stats* stats, int64_t out[3]);
+
 const char* rt_last_error(void);
 int rt_abi_version(void);
 int rt_device_count(void);

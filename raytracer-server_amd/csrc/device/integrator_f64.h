@@ -99,13 +99,19 @@ struct CameraSample {
     V3 d;
     uint64_t r0, r1;
 };
+// (seed: a.seed for a frame or a pixel list; the unit's own pass seed in a batched render)
 template <bool G1 = false>
-RT_DEV CameraSample camera_sample(const DevScene& sc, const RenderArgs& a, const SubPixel& sp, int smp) {
-    Rng rng(a.seed, sp.pid, (uint32_t)smp, (uint32_t)sp.sub);
+RT_DEV CameraSample camera_sample_seeded(const DevScene& sc, const RenderArgs& a, const SubPixel& sp, int smp,
+                                         uint64_t seed) {
+    Rng rng(seed, sp.pid, (uint32_t)smp, (uint32_t)sp.sub);
     double u1 = rng.uniform(), u2 = rng.uniform();
     const Ray r = camera_ray<G1>(sc, ld3(a.cx), ld3(a.cy), (double)a.width, (double)a.height, sp.col, sp.yref, sp.sx, sp.sy,
                              u1, u2);
     return CameraSample{r.d, rng.s0, rng.s1};
+}
+template <bool G1 = false>
+RT_DEV CameraSample camera_sample(const DevScene& sc, const RenderArgs& a, const SubPixel& sp, int smp) {
+    return camera_sample_seeded<G1>(sc, a, sp, smp, a.seed);
 }
 // New camera path from a camera sample.
 RT_DEV void begin_path(const DevScene& sc, const CameraSample& cs, PathState& ps) {

@@ -39,4 +39,27 @@ hipError_t launch_accum_select(const double* S, const float* var, const uint32_t
 hipError_t launch_accum_holes(const uint32_t* cnt, int width, int height, int32_t period, int32_t phase, void* scratch,
                               uint32_t* out, long cap, uint32_t* total, unsigned long long* n_holes, hipStream_t st);
 
+// Batched passes (rt_ffi.h rt_accum_plan). The most passes one entry may hold: the pass index rides in
+// the top 4 bits of a unit word (render_f64.hip kPassShift).
+constexpr int kPassesMax = 16;
+// The plan's first two passes: the selection's ballots and scanned block offsets in `scratch` (as launch_accum_select
+// leaves them), want[pix] = the pass count each active pixel wants before the frame cap (0: inactive),
+// hist[kPassesMax + 1] = how many pixels want each count, *total = the list's length (all device).
+hipError_t launch_accum_plan_count(const double* S, const float* var, const uint32_t* cnt, int64_t N, int width,
+                                   int height, float abs_tol, float rel_tol, int32_t max_n, int32_t n, float gain,
+                                   int32_t max_passes, void* scratch, uint8_t* want, uint32_t* hist, uint32_t* total,
+                                   hipStream_t st);
+// The plan's last pass: out[at] = the id and counts[at] = min(want, cmax) of the active pixels, ascending, at most cap.
+hipError_t launch_accum_plan_write(const void* scratch, const uint8_t* want, long npix, int32_t cmax, uint32_t* out,
+                                   uint8_t* counts, long cap, hipStream_t st);
+// A list with counts -> off[e] (nullable), the exclusive prefix sum of counts, and units[off[e] + i] =
+// list[e] | i << 28 (at most cap words); *total = the unit count. scratch: runs_scratch_bytes(n) bytes.
+size_t runs_scratch_bytes(long n);
+hipError_t launch_accum_expand(const uint32_t* list, const uint8_t* counts, long n, void* scratch, uint32_t* off,
+                               uint32_t* units, long cap, uint32_t* total, hipStream_t st);
+// The run merge: entry e's counts[e] units m[off[e] + i][4][3], in pass order, into pixel list[e] with
+// launch_accum_add_list's expression; cnt[p] += (counts[e], counts[e] n).
+hipError_t launch_accum_add_runs(double* S, double* Q, uint32_t* cnt, const uint32_t* list, const uint8_t* counts,
+                                 const uint32_t* off, long n_list, const double* m, int32_t n, hipStream_t st);
+
 }  // namespace rt

@@ -5,6 +5,7 @@
 //                       whose frame kernel has no list instance (Phong mesh scenes, octrees without slot tables) or
 //                       whose list is short; launch_render_list_f64 hands the other mesh scenes' lists to the list
 //                       instances of the frame's own pool kernels, which give the same bits.
+//   k_render_passes_f64 — the same loop over a list of (pixel, pass) units with a seed per pass.
 //   k_trace_f64       — Scene::trace_ray for a batch of rays (parity tests of the intersectors).
 //   wavefront kernels — see wavefront_f64.hip.
 #include <hip/hip_runtime.h>
@@ -71,10 +72,20 @@ __device__ unsigned long long g_dbg_wave[kDbgWaveRec * kDbgWaves];
 // 1.7% (cubes) slower; with the register alone 0.9% and 0.4%. Every read is made by an active lane: it holds a
 // ticket < nunits, so its id < n_whole = 4 n_pixels. (unit_of also runs for a lane whose ticket is past the end, or
 // -1 after a stop: that id is out of range, but the lane is inactive from then on and load_pix(active) reads nothing.)
-template <int F, bool L>
+// L = kPasses (k_render_passes_f64): the list holds one word per unit-group, a (pixel, pass) pair packed
+// as pixel | pass << kPassShift; units[id >> 2] is loaded exactly where a list instance loads pixels[id >> 2], and
+// the camera sample draws from seeds[pass] (16 u64 on the device) instead of a.seed. The camera ring only reads ahead
+// within one unit, so the seed is a per-unit fact as the pixel is; nothing else in the loop knows about passes. The
+// pass rides in the top 4 bits of the pixel's register (frames of width * height < 2^28: the host checks), so the
+// instance needs no register beyond the list's; the seed is an 8-byte load beside the camera sample's arithmetic.
+constexpr int kFrame = 0, kList = 1, kPasses = 2;
+constexpr int kPassShift = 28;
+constexpr uint32_t kPassPixMask = (1u << kPassShift) - 1u;
+template <int F, int L>
 __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
                                            uint32_t* next_sub, long nsub, int refill,
-                                           const uint32_t* __restrict__ pixels) {
+                                           const uint32_t* __restrict__ pixels,
+                                           const uint64_t* __restrict__ seeds = nullptr) {
     // Compact scenes (<= kMaxCompactObjects objects): the object table is copied into LDS, so the
     // shading's per-lane object reads (hit object, light) are ds_reads instead of global loads.
     // the fused mesh instances (F odd) keep the one-ballot guards (path_f64.h kCfgGuards1: they sit at their
@@ -164,9 +175,13 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
                 if (now || (refill > 0 && need)) {
                     RT_DBG_REGION(3);
                     SubPixel sp;
-                    if constexpr (L) sp = subpixel_of_pixel(a, pix, id);
+                    if constexpr (L == kPasses) sp = subpixel_of_pixel(a, pix & kPassPixMask, id);
+                    else if constexpr (L) sp = subpixel_of_pixel(a, pix, id);
                     else sp = subpixel_of(a, id);
-                    const CameraSample nb = camera_sample<C::g1>(sc, a, sp, now ? s : s + nbuf + 1);
+                    CameraSample nb;
+                    if constexpr (L == kPasses)
+                        nb = camera_sample_seeded<C::g1>(sc, a, sp, now ? s : s + nbuf + 1, seeds[pix >> kPassShift]);
+                    else nb = camera_sample<C::g1>(sc, a, sp, now ? s : s + nbuf + 1);
                     if (now) {
                         begin_path(sc, nb, ps);
                         fresh = false;
@@ -309,14 +324,23 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
 template <int F, int W>
 __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                           uint32_t* next_sub, long nsub, int refill) {
-    fused_body<F, false>(sc_g, a_g, sub_buf, next_sub, nsub, refill, nullptr);
+    fused_body<F, kFrame>(sc_g, a_g, sub_buf, next_sub, nsub, refill, nullptr);
 }
 // The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
 template <int F, int W>
 __global__ __launch_bounds__(256, W) void k_render_list_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                            uint32_t* next_sub, long nsub, int refill,
                                                            const uint32_t* __restrict__ pixels) {
-    fused_body<F, true>(sc_g, a_g, sub_buf, next_sub, nsub, refill, pixels);
+    fused_body<F, kList>(sc_g, a_g, sub_buf, next_sub, nsub, refill, pixels);
+}
+// The batched-passes instance: nsub = 4 n_units units, units[u] = pixel | pass << 28 (pass < 16),
+// seeds[16] on the device, sub_buf the compact [n_units][4][3] buffer. Scheduling is the list instance's.
+template <int F, int W>
+__global__ __launch_bounds__(256, W) void k_render_passes_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
+                                                             uint32_t* next_sub, long nsub, int refill,
+                                                             const uint32_t* __restrict__ units,
+                                                             const uint64_t* __restrict__ seeds) {
+    fused_body<F, kPasses>(sc_g, a_g, sub_buf, next_sub, nsub, refill, units, seeds);
 }
 
 // Split tail: subpixel n_whole + j's mean, continuing the sequential sum chunk 0 left in sub_buf (its lane
@@ -667,6 +691,43 @@ hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a_in, co
         return launch_render_list_roles_f64(sc, a, pixels, n_pixels, sub_buf, next_unit, tail_buf, tail_cap, st);
     }
     launch_mk_features<true>(0, sc, a, sub_buf, next_unit, a.n_whole, nullptr, 0, pixels, st);
+    return hipGetLastError();
+}
+
+// Batched passes: the fused body's kPasses instance of a.features & 15 over n_units (pixel, pass)
+// words; mesh instances at 3 waves/SIMD and analytic ones at RT_MK_W4, planned like a pixel list (plan_units, no
+// split tail). Only the fused family has this instance.
+template <int F>
+static void launch_mk_passes(const DevScene& sc, RenderArgs a, double* sub_buf, uint32_t* next_unit, int refill,
+                             const uint32_t* units, const uint64_t* seeds, hipStream_t st) {
+    constexpr int W = (F & 1) ? 3 : RT_MK_W4;
+    const long nsub = a.n_whole;
+    const long blocks = resident_blocks(k_render_passes_f64<F, W>, (nsub + 255) / 256);
+    plan_units(a, blocks * 256, 256, RT_MK_MIN_RUN);
+    hipLaunchKernelGGL((k_render_passes_f64<F, W>), dim3((unsigned)blocks), dim3(256), 0, st, sc, a, sub_buf, next_unit,
+                       nsub, refill, units, seeds);
+}
+hipError_t launch_render_passes_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* units, long n_units,
+                                    const uint64_t* seeds, double* sub_buf, uint32_t* next_unit, hipStream_t st) {
+    if (n_units <= 0 || a_in.n_samples <= 0) return hipSuccess;
+    if (n_units > 0x7fffffffL / 4 || (long)a_in.width * a_in.height > (long)kPassPixMask || !units || !seeds)
+        return hipErrorInvalidValue;
+    RenderArgs a = a_in;
+    a.n_whole = (int32_t)(n_units * 4);
+    a.chunk_lg = 0;
+    a.tail_cps = 1;
+    a.tail_buf = nullptr;
+    t_tail_plan = TailPlan{};
+    hipError_t e = hipMemsetAsync(next_unit, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    const int refill = cam_refill();
+#define RT_MP_CASE(F) case F: launch_mk_passes<F>(sc, a, sub_buf, next_unit, refill, units, seeds, st); break;
+    switch (a.features & 15) {
+        RT_MP_CASE(0) RT_MP_CASE(1) RT_MP_CASE(2) RT_MP_CASE(3) RT_MP_CASE(4) RT_MP_CASE(5) RT_MP_CASE(6)
+        RT_MP_CASE(7) RT_MP_CASE(8) RT_MP_CASE(9) RT_MP_CASE(10) RT_MP_CASE(11) RT_MP_CASE(12) RT_MP_CASE(13)
+        RT_MP_CASE(14) RT_MP_CASE(15)
+    }
+#undef RT_MP_CASE
     return hipGetLastError();
 }
 

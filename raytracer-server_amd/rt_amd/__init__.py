@@ -30,6 +30,7 @@ LIB_PATH = os.environ.get("RT_AMD_LIB") or os.path.join(os.path.dirname(_HERE), 
 
 RT_OK = 0
 RT_CANCELLED = 1
+PASSES_MAX = 16  # RT_PASSES_MAX: the most passes per pixel of a batched render
 FLAG_MIS = 1 << 0
 FLAG_MEGAKERNEL = 1 << 1
 FLAG_FP32 = 1 << 2
@@ -99,7 +100,8 @@ _EXPORTS = ["rt_scene_load_toml", "rt_scene_create", "rt_scene_destroy", "rt_sce
             "rt_accum_add_sub_pixels", "rt_accum_add_sub_pixels_device", "rt_accum_counts", "rt_accum_select",
             "rt_accum_select_device", "rt_scene_view", "rt_scene_get_view", "rt_accum_reproject", "rt_accum_holes",
             "rt_accum_holes_device", "rt_accum_fill", "rt_render_pixels_path", "rt_render_pixels_with",
-            "rt_render_pixels_with_device"]
+            "rt_render_pixels_with_device", "rt_render_pixel_passes", "rt_render_pixel_passes_device", "rt_accum_plan",
+            "rt_accum_plan_device", "rt_accum_add_passes", "rt_accum_refine"]
 
 
 def _load():
@@ -164,6 +166,15 @@ def _load():
     L.rt_accum_holes.argtypes = [vp, I, I, P(U32), I64, P(I64), P(I64)]
     L.rt_accum_holes_device.argtypes = [vp, I, I, vp, I64, P(I64), P(I64), vp]
     L.rt_accum_fill.argtypes = [vp, vp, P(RenderParams), ctypes.c_uint64, I, I, P(I), P(RenderStats), P(I64)]
+    U8, U64 = ctypes.c_uint8, ctypes.c_uint64
+    L.rt_render_pixel_passes.argtypes = [vp, P(RenderParams), P(U32), P(U8), I64, P(U64), I, P(U8), P(D), P(I),
+                                         P(RenderStats)]
+    L.rt_render_pixel_passes_device.argtypes = [vp, P(RenderParams), vp, vp, I64, I64, P(U64), I, vp, vp, vp,
+                                                P(RenderStats)]
+    L.rt_accum_plan.argtypes = [vp, F, F, I, I, F, I, P(U32), P(U8), I64, P(I64), P(I64), P(I64)]
+    L.rt_accum_plan_device.argtypes = [vp, F, F, I, I, F, I, vp, vp, I64, P(I64), P(I64), P(I64), vp]
+    L.rt_accum_add_passes.argtypes = [vp, vp, P(RenderParams), P(U64), I, P(U32), P(U8), I64, P(I), P(RenderStats)]
+    L.rt_accum_refine.argtypes = [vp, vp, P(RenderParams), F, F, I, F, P(U64), I, P(I), P(RenderStats), P(I64)]
     L.rt_last_error.restype = ctypes.c_char_p
     L.rt_last_error.argtypes = []
     L.rt_abi_version.argtypes = []
@@ -655,6 +666,58 @@ class Accumulator:
         out["cancelled"] = rc == RT_CANCELLED
         return out
 
+    def plan(self, abs_tol, rel_tol=0.0, max_n=0, n=4, gain=1.0, max_passes=PASSES_MAX, cap=None):
+        """select plus a pass count per listed pixel (rt_accum_plan): how many passes of n samples per
+        subpixel each active pixel should get at once, gain * (N_p g_p / thr^2 - N_p) / n rounded up, within
+        1 .. max_passes, clipped by max_n and by a frame's worth of units in all. Returns (ids uint32, counts uint8,
+        info) with info = dict(pixels, units, passes): the list's full length, the sum of the counts and the largest
+        count."""
+        cap = self.width * self.height if cap is None else cap
+        ids = np.zeros(max(1, cap), dtype=np.uint32)
+        cnt = np.zeros(max(1, cap), dtype=np.uint8)
+        n_out, units, passes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(lib.rt_accum_plan(self._h, abs_tol, rel_tol, max_n, n, gain, max_passes, _ptr(ids, ctypes.c_uint32),
+                                 _ptr(cnt, ctypes.c_uint8), cap, ctypes.byref(n_out), ctypes.byref(units),
+                                 ctypes.byref(passes)))
+        m = min(n_out.value, cap)
+        return ids[:m], cnt[:m], dict(pixels=n_out.value, units=units.value, passes=passes.value)
+
+    def add_passes(self, scene, pixels, counts, spp, seeds, mis=False, cancel=None):
+        """Renders counts[e] passes of pixel pixels[e] at `spp`, pass i with seeds[i], in one launch and merges them in
+        pass order (rt_accum_add_passes): bit for bit what add_pixels of {e : counts[e] > i} with seeds[i] gives, pass
+        by pass. Returns the render's stats; stats["cancelled"] is True when nothing was merged."""
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        ct = np.ascontiguousarray(counts, dtype=np.uint8).reshape(-1)
+        if ct.size != px.size:
+            raise ValueError(f"Accumulator.add_passes: {ct.size} counts for {px.size} pixels")
+        sd = np.ascontiguousarray([int(x) % (1 << 64) for x in seeds], dtype=np.uint64)
+        p = make_params(self.width, self.height, spp, 0, None, FLAG_MEGAKERNEL | (FLAG_MIS if mis else 0),
+                        self.device, 1)
+        st = RenderStats()
+        rc = _check(lib.rt_accum_add_passes(self._h, scene.handle, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), sd.size,
+                                            _ptr(px, ctypes.c_uint32), _ptr(ct, ctypes.c_uint8), px.size,
+                                            ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st)))
+        out = st.as_dict()
+        out["cancelled"] = rc == RT_CANCELLED
+        return out
+
+    def refine(self, scene, spp, seeds, abs_tol, rel_tol=0.0, max_n=0, gain=1.0, mis=False, cancel=None):
+        """plan(abs_tol, rel_tol, max_n, n = spp // 4, gain, max_passes = len(seeds)) followed by add_passes of the
+        planned lists, which stay on the device (rt_accum_refine). Returns the render's stats with
+        stats["refine"] = (pixels, units, passes used); an empty plan launches nothing."""
+        sd = np.ascontiguousarray([int(x) % (1 << 64) for x in seeds], dtype=np.uint64)
+        p = make_params(self.width, self.height, spp, 0, None, FLAG_MEGAKERNEL | (FLAG_MIS if mis else 0),
+                        self.device, 1)
+        st = RenderStats()
+        out3 = (ctypes.c_int64 * 3)()
+        rc = _check(lib.rt_accum_refine(self._h, scene.handle, ctypes.byref(p), abs_tol, rel_tol, max_n, gain,
+                                        _ptr(sd, ctypes.c_uint64), sd.size,
+                                        ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st), out3))
+        out = st.as_dict()
+        out["refine"] = (int(out3[0]), int(out3[1]), int(out3[2]))
+        out["cancelled"] = rc == RT_CANCELLED
+        return out
+
 
 def look_at(pos, target, up=(0.0, 1.0, 0.0), fov=0.5135):
     """The arguments of Scene.view for a camera at pos looking at target: dict(pos, dir, right, fov) with
@@ -682,6 +745,32 @@ def render_pixels(scene, width, height, pixels, spp, seed=0x5EED, mis=False, dev
     rc = _check(lib.rt_render_pixels_with(scene.handle, ctypes.byref(p), _ptr(px, ctypes.c_uint32), px.size, path,
                                           _ptr(rgb, ctypes.c_uint8), _ptr(sub, ctypes.c_double),
                                           ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st)))
+    out = st.as_dict()
+    out["cancelled"] = rc == RT_CANCELLED
+    return rgb, sub, out
+
+
+def render_pixel_passes(scene, width, height, pixels, counts, spp, seeds, mis=False, device=0, want_sub=False,
+                        want_rgb=True, cancel=None):
+    """render_pixels with counts[e] passes of pixel pixels[e] in one launch, pass i drawing from seeds[i]
+    (rt_render_pixel_passes; counts in 1 .. len(seeds) <= PASSES_MAX, at most width * height units in
+    all). Returns (rgb[units, 3] u8 or None, sub[units, 4, 3] f64 or None, stats), indexed by unit-group
+    off[e] + i with off the exclusive prefix sum of counts; each is what render_pixels gives that pixel for
+    seeds[i], bit for bit."""
+    px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+    ct = np.ascontiguousarray(counts, dtype=np.uint8).reshape(-1)
+    if ct.size != px.size:
+        raise ValueError(f"render_pixel_passes: {ct.size} counts for {px.size} pixels")
+    sd = np.ascontiguousarray([int(x) % (1 << 64) for x in seeds], dtype=np.uint64)
+    units = int(ct.astype(np.int64).sum())
+    p = make_params(width, height, spp, 0, None, FLAG_MEGAKERNEL | (FLAG_MIS if mis else 0), device, 1)
+    rgb = np.zeros((units, 3), dtype=np.uint8) if want_rgb else None
+    sub = np.zeros((units, 4, 3), dtype=np.float64) if want_sub else None
+    st = RenderStats()
+    rc = _check(lib.rt_render_pixel_passes(scene.handle, ctypes.byref(p), _ptr(px, ctypes.c_uint32),
+                                           _ptr(ct, ctypes.c_uint8), px.size, _ptr(sd, ctypes.c_uint64), sd.size,
+                                           _ptr(rgb, ctypes.c_uint8), _ptr(sub, ctypes.c_double),
+                                           ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st)))
     out = st.as_dict()
     out["cancelled"] = rc == RT_CANCELLED
     return rgb, sub, out
@@ -771,20 +860,29 @@ def render_progressive(scene, width, height, spp, first=8, seed=0x5EED, device=0
 ERROR_TARGET_DEFAULTS = dict(abs_tol=0.04, rel_tol=0.0, first=16, pass_spp=16)
 
 
+# The measured choice of render_to_error's batch and gain (batch stays 0 by default: the sequential
+# loop). Pass them as render_to_error(..., **ERROR_TARGET_BATCH_DEFAULTS).
+ERROR_TARGET_BATCH_DEFAULTS = dict(batch=8, gain=1.0)
+
+
 def pass_seed(seed, k):
     """The seed of pass k of render_progressive and render_to_error."""
     return (seed + k * PASS_SEED_STEP) % (1 << 64)
 
 
 def render_to_error(scene, width, height, abs_tol=None, max_spp=512, first=None, pass_spp=None, seed=0x5EED,
-                    rel_tol=None, device=0, cancel=None, **denoise_params):
+                    rel_tol=None, device=0, cancel=None, batch=0, gain=None, **denoise_params):
     """A generator that refines a frame until every pixel's estimated standard error (the 3 x 3 tent of the
     accumulator's variance) is below abs_tol + rel_tol * luminance / 3, or holds max_spp samples. It yields
     (rgb[h, w, 3] u8, mean spp, active fraction) after the two full passes of first / 2 and after every sparse pass of
     pass_spp over the pixels Accumulator.select returned (max_n = max_spp // 4 enforces the budget); pass k renders
     with pass_seed(seed, k). Each frame is filtered with denoise_var on the per-pixel-count variance (denoise_params:
     levels / sigma_*, DENOISE_VAR_DEFAULTS otherwise). Parameters left None come from ERROR_TARGET_DEFAULTS. A raised
-    cancel word ends the generator."""
+    cancel word ends the generator.
+    batch = C > 0 (at most PASSES_MAX) runs up to C passes per pixel in one launch (Accumulator.refine):
+    a batch plans gain (None: ERROR_TARGET_BATCH_DEFAULTS) of each active pixel's predicted need, pass i of the batch
+    renders with pass_seed(seed, k + i), k advances by the passes used, and the generator yields after every batch.
+    batch = 0 is the sequential loop."""
     d = ERROR_TARGET_DEFAULTS
     abs_tol = d["abs_tol"] if abs_tol is None else abs_tol
     rel_tol = d["rel_tol"] if rel_tol is None else rel_tol
@@ -799,6 +897,21 @@ def render_to_error(scene, width, height, abs_tol=None, max_spp=512, first=None,
                 return
         feat = render_features(scene, width, height, device=device)
         k = 2
+        if batch:
+            gain = ERROR_TARGET_BATCH_DEFAULTS["gain"] if gain is None else gain
+            n_active = acc.select(abs_tol, rel_tol, max_n, cap=0)[1]
+            while True:
+                sub, var, _ = acc.resolve(want_var=True, want_rgb=False)
+                mean_spp = 4.0 * float(acc.counts()[1].mean())
+                yield denoise_var(sub, feat, var, device=device, **denoise_params), mean_spp, n_active / npix
+                if n_active == 0:
+                    return
+                st = acc.refine(scene, pass_spp, [pass_seed(seed, k + i) for i in range(batch)], abs_tol, rel_tol, max_n,
+                                gain, cancel=cancel)
+                if st["cancelled"]:
+                    return
+                k += st["refine"][2]
+                n_active = acc.select(abs_tol, rel_tol, max_n, cap=0)[1]
         while True:
             ids, _ = acc.select(abs_tol, rel_tol, max_n)
             sub, var, _ = acc.resolve(want_var=True, want_rgb=False)

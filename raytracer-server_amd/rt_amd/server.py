@@ -17,6 +17,9 @@ Run:  PORT=8080 python -m rt_amd.server <scenes dir>
       frame re-sent with the same chunk messages).
       RT_TARGET_ERROR=<abs_tol> selects jobs rendered to a per-pixel error target (rt_amd.render_to_error, DESIGN.md
       §13): RT_PROGRESSIVE gives the first frame's spp, the request's spp is the per-pixel budget.
+      RT_TARGET_BATCH=<C>[,<gain>] together with RT_TARGET_ERROR: up to <C> (1..16) sparse passes per pixel run in one
+      launch, each batch handing out <gain> (in (0, 1]; default: rt_amd.ERROR_TARGET_BATCH_DEFAULTS) of a pixel's
+      predicted need (rt_amd.render_to_error's batch and gain). Unset: the sequential loop.
       RT_REPROJECT=<max_n> together with RT_PROGRESSIVE or RT_TARGET_ERROR: a connection keeps its last accumulator
       and view, and a request for the same scene starts from the reprojected history (rt_amd.render_interactive,
       DESIGN.md §14; at most max_n samples per subpixel are inherited).
@@ -91,6 +94,21 @@ def parse_fill(text):
     if spp < 4 or refresh < 0:
         raise ValueError(f"bad RT_REPROJECT_FILL {text!r}: spp must be >= 4 and refresh >= 0")
     return spp, refresh
+
+
+def parse_batch(text):
+    """RT_TARGET_BATCH's value "<C>[,<gain>]" as (batch, gain); (0, None) for None (unset: the sequential loop), gain
+    None when only C is given. ValueError for anything but an integer C in 1 .. 16 and a gain in (0, 1]."""
+    if text is None:
+        return 0, None
+    parts = text.split(",")
+    if len(parts) not in (1, 2):
+        raise ValueError(f"bad RT_TARGET_BATCH {text!r}")
+    batch = int(parts[0])
+    gain = float(parts[1]) if len(parts) == 2 else None
+    if batch < 1 or batch > 16 or (gain is not None and not 0.0 < gain <= 1.0):
+        raise ValueError(f"bad RT_TARGET_BATCH {text!r}: C must be in 1 .. 16 and gain in (0, 1]")
+    return batch, gain
 
 
 def gpu_band_renderer(device=0, fp32=False):
@@ -212,11 +230,12 @@ class AdaptiveJob:
     ProgressiveJob does. RenderJob's interface: a stop takes effect between passes, and inside a pass through the cancel
     word."""
 
-    def __init__(self, send, abs_tol, first=16, device=0, **denoise_params):
+    def __init__(self, send, abs_tol, first=16, device=0, batch=0, gain=None, **denoise_params):
         self.send = send
         self.abs_tol = abs_tol
         self.first = first
         self.device = device
+        self.batch, self.gain = batch, gain  # RT_TARGET_BATCH: passed on to render_to_error only when set
         self.denoise_params = denoise_params
         self.cancel = ctypes.c_int32(1)  # starts cancelled == not running
 
@@ -232,9 +251,14 @@ class AdaptiveJob:
 
         self.cancel.value = 0
         loop = asyncio.get_running_loop()
+        batched = {}
+        if self.batch:
+            batched["batch"] = self.batch
+            if self.gain is not None:
+                batched["gain"] = self.gain
         frames = rt_amd.render_to_error(scene, width, height, abs_tol=self.abs_tol, max_spp=max(spp, self.first),
                                         first=self.first, seed=seed, device=self.device, cancel=self.cancel,
-                                        **self.denoise_params)
+                                        **batched, **self.denoise_params)
         try:
             while True:
                 if self.cancel.value:
@@ -443,9 +467,11 @@ def main(argv=None):
         # rendering to an error target: whole frames, sparse passes over the pixels still above it
         abs_tol = float(os.environ["RT_TARGET_ERROR"])
         first = int(os.environ.get("RT_PROGRESSIVE", rt_amd.ERROR_TARGET_DEFAULTS["first"]))
+        batch, gain = parse_batch(os.environ.get("RT_TARGET_BATCH"))
         print(f"RT_TARGET_ERROR={abs_tol}: whole-frame jobs rendered to a per-pixel error target, first frame at "
-              f"{first} spp, the request's spp as the per-pixel budget", file=sys.stderr)
-        server = Server(scenes, job_factory=lambda send: AdaptiveJob(send, abs_tol, first=first))
+              f"{first} spp, the request's spp as the per-pixel budget"
+              + (f"; RT_TARGET_BATCH: up to {batch} passes per pixel in one launch" if batch else ""), file=sys.stderr)
+        server = Server(scenes, job_factory=lambda send: AdaptiveJob(send, abs_tol, first=first, batch=batch, gain=gain))
     elif "RT_PROGRESSIVE" in os.environ:
         # progressive refinement: whole frames, each refined frame re-sent with the same chunk messages
         first = int(os.environ["RT_PROGRESSIVE"])

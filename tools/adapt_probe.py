@@ -18,6 +18,14 @@
       and max spp, passes, and the linear RMSE against a 4096-spp frame of seed 999 over that of a uniform accumulation
       with the same pass sizes taken to the first total at or above the mean spp. These figures choose
       rt_amd.ERROR_TARGET_DEFAULTS.
+  python tools/adapt_probe.py batch [--size 1920x1080] [--scenes cornell_box,cubes,flying_unicorn] [--batch C --gain g]
+                                    [--log profiles/batch_time.log]
+      DESIGN.md §17: the sequential error-target loop (rt_accum_select_device, rt_render_pixels_device with the scene's
+      own list family, rt_accum_add_sub_pixels_device) and the batched one (rt_accum_refine: the fused body's
+      k_render_passes_f64) side by side in one process, a step of each in turn, on two accumulators that start from the
+      same two 8-spp passes; abs_tol 0.04, pass_spp 16, max_spp 496. Per loop: render launches, the wall time from the
+      first selection to the last merge (every call waits for its work), the renders' device time (HIP events around
+      the render kernels, rt_render_stats.device_ms), Msamples/s per launch (median, first, last), mean spp.
 """
 import argparse
 import ctypes
@@ -272,6 +280,95 @@ def cmd_target(args):
                 f"{rmse_a:14.5f} {rmse_u:13.5f} ({spp:3d}) {rmse_a / rmse_u:6.3f}")
 
 
+def cmd_batch(args):
+    import time
+
+    if rt_amd.device_count() < 1:
+        raise RuntimeError("adapt_probe: no HIP device visible (it measures on the GPU only)")
+    log = Log(args.log)
+    w, h = _size(args.size)
+    npix, spp, abs_tol, max_n, seed = w * h, 16, 0.04, 496 // 4, 77
+    d = rt_amd.ERROR_TARGET_BATCH_DEFAULTS
+    C = args.batch if args.batch else d["batch"]
+    gain = args.gain if args.gain else d["gain"]
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+    st = V(stream) if stream else None
+    ids_d = torch.zeros(npix, dtype=torch.int32, device=dev)
+    lsub = torch.zeros(npix * 12, dtype=torch.float64, device=dev)
+    log(f"# adapt_probe batch: {w}x{h}, abs_tol {abs_tol}, two 8-spp passes, then passes of {spp} spp to max_spp 496; "
+        f"batched: C = {C}, gain = {gain}; seeds pass_seed({seed}, k); one process, a step of each loop in turn")
+    log("scene            loop        list family  launches  wall ms  render ms  Ms/s per launch median (first, last)  "
+        "mean spp")
+    for name in args.scenes.split(","):
+        sc = _scene(name)
+        fam = FAMILY_NAMES[rt_amd.render_pixels_path(sc, w, h, spp, npix)[0]]
+        p = rt_amd.make_params(w, h, spp, 0, None, rt_amd.FLAG_MEGAKERNEL, 0, 1)
+        seq, bat = rt_amd.Accumulator(w, h), rt_amd.Accumulator(w, h)
+        for acc in (seq, bat):
+            acc.add(sc, 8, rt_amd.pass_seed(seed, 0))
+            acc.add(sc, 8, rt_amd.pass_seed(seed, 1))
+        # warm-up on a third accumulator: both paths' kernels loaded, the workspaces allocated
+        with rt_amd.Accumulator(w, h) as warm:
+            warm.add(sc, 8, 1)
+            warm.add(sc, 8, 2)
+            ids, _ = warm.select(abs_tol, 0.0, max_n)
+            warm.add_pixels(sc, ids, spp, 3)
+            warm.refine(sc, spp, [4, 5], abs_tol, 0.0, max_n, gain)
+        torch.cuda.synchronize()
+        stats = rt_amd.RenderStats()
+        n_out = ctypes.c_int64()
+        run = {"sequential": dict(k=2, wall=0.0, ms=[], samples=[], done=False),
+               "batched": dict(k=2, wall=0.0, ms=[], samples=[], done=False)}
+
+        def step_seq(r):
+            t0 = time.perf_counter()
+            rt_amd._check(rt_amd.lib.rt_accum_select_device(seq.handle, abs_tol, 0.0, max_n, V(ids_d.data_ptr()), npix,
+                                                            ctypes.byref(n_out), st))
+            n = n_out.value
+            if n:
+                p.seed = rt_amd.pass_seed(seed, r["k"])
+                rt_amd._check(rt_amd.lib.rt_render_pixels_device(sc.handle, ctypes.byref(p), V(ids_d.data_ptr()), n, None,
+                                                                 V(lsub.data_ptr()), st, ctypes.byref(stats)))
+                rt_amd._check(rt_amd.lib.rt_accum_add_sub_pixels_device(seq.handle, V(ids_d.data_ptr()), n,
+                                                                        V(lsub.data_ptr()), spp // 4, st))
+                r["k"] += 1
+            r["wall"] += time.perf_counter() - t0
+            return n, stats.device_ms, stats.samples
+
+        def step_bat(r):
+            t0 = time.perf_counter()
+            out = bat.refine(sc, spp, [rt_amd.pass_seed(seed, r["k"] + i) for i in range(C)], abs_tol, 0.0, max_n, gain)
+            r["wall"] += time.perf_counter() - t0
+            r["k"] += out["refine"][2]
+            return out["refine"][0], out["device_ms"], out["samples"]
+
+        while not (run["sequential"]["done"] and run["batched"]["done"]):
+            for key, fn in (("sequential", step_seq), ("batched", step_bat)):
+                r = run[key]
+                if r["done"]:
+                    continue
+                n, ms, samples = fn(r)
+                if n == 0 or len(r["ms"]) >= 400:
+                    r["done"] = True
+                else:
+                    r["ms"].append(ms)
+                    r["samples"].append(samples)
+        for key, acc in (("sequential", seq), ("batched", bat)):
+            r = run[key]
+            rates = [s_ / m / 1e3 for s_, m in zip(r["samples"], r["ms"]) if m > 0]
+            mean_spp = 4.0 * float(acc.counts()[1].mean())
+            log(f"{name:16s} {key:11s} {fam if key == 'sequential' else 'fused':11s} {len(r['ms']):9d} "
+                f"{r['wall'] * 1e3:8.1f} {sum(r['ms']):10.1f}  {statistics.median(rates):10.1f} ({rates[0]:.1f}, "
+                f"{rates[-1]:.1f})" + " " * 12 + f"{mean_spp:8.2f}")
+        s_, b_ = run["sequential"], run["batched"]
+        log(f"{name}: batched / sequential wall time {b_['wall'] / s_['wall']:.3f}, render time "
+            f"{sum(b_['ms']) / sum(s_['ms']):.3f}, launches {len(b_['ms'])} / {len(s_['ms'])}")
+        seq.close()
+        bat.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sp = ap.add_subparsers(dest="cmd", required=True)
@@ -287,6 +384,13 @@ def main():
     g.add_argument("--size", default="96x72")
     g.add_argument("--log", default=os.path.join(REPO, "profiles", "adapt_target.log"))
     g.set_defaults(fn=cmd_target)
+    b = sp.add_parser("batch")
+    b.add_argument("--size", default="1920x1080")
+    b.add_argument("--scenes", default="cornell_box,cubes,flying_unicorn")
+    b.add_argument("--batch", type=int, default=0, help="C (default: rt_amd.ERROR_TARGET_BATCH_DEFAULTS)")
+    b.add_argument("--gain", type=float, default=0.0)
+    b.add_argument("--log", default=os.path.join(REPO, "profiles", "batch_time.log"))
+    b.set_defaults(fn=cmd_batch)
     args = ap.parse_args()
     args.fn(args)
 
