@@ -346,6 +346,20 @@ extern "C" {
         n_pixels: i64, units: i64, seeds: *const u64, n_seeds: i32, d_rgb: *mut c_void, d_sub: *mut c_void,
         stream: *mut c_void, stats: *mut RtRenderStats,
     ) -> c_int;
+    /// `rt_render_pixel_passes` with the kernel family chosen by the caller (`RT_LIST_*`), by
+    /// `rt_render_pixels_with`'s rules: `RT_LIST_AUTO` is the plain call; a family the scene has no instance of is
+    /// `RT_E_INVAL` before any device call. Same bits whichever family runs.
+    pub fn rt_render_pixel_passes_with(
+        scene: *const RtScene, params: *const RtRenderParams, pixels: *const u32, counts: *const u8, n_pixels: i64,
+        seeds: *const u64, n_seeds: i32, path: i32, rgb_out: *mut u8, sub_out: *mut f64, cancel: *const i32,
+        stats: *mut RtRenderStats,
+    ) -> c_int;
+    /// `rt_render_pixel_passes_device` with the family chosen by the caller, by the same rules.
+    pub fn rt_render_pixel_passes_with_device(
+        scene: *const RtScene, params: *const RtRenderParams, d_pixels: *const c_void, d_counts: *const c_void,
+        n_pixels: i64, units: i64, seeds: *const u64, n_seeds: i32, path: i32, d_rgb: *mut c_void,
+        d_sub: *mut c_void, stream: *mut c_void, stats: *mut RtRenderStats,
+    ) -> c_int;
     /// `rt_accum_select` plus a pass count per listed pixel (`n` samples per subpixel per pass, `gain` in (0, 1],
     /// `max_passes` in 1 ..= `RT_PASSES_MAX`), capped to a frame's worth of units in all.
     pub fn rt_accum_plan(

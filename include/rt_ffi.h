@@ -20,6 +20,9 @@
  *                          target with sparse pixel-list passes)
  *   rt_render_pixels_path, rt_render_pixels_with: no counterpart either (which kernel family runs a pixel list of
  *                          a mesh scene: the pool kernel of its full frame, or the fused per-lane walk)
+ *   rt_render_pixel_passes, rt_render_pixel_passes_with, rt_accum_plan, rt_accum_add_passes, rt_accum_refine: no
+ *                          counterpart either (several error-target passes per pixel in one launch, by the same
+ *                          families)
  *   rt_scene_view, rt_accum_reproject: no counterpart either (camera views of one scene, and an accumulator's
  *                          history carried across a camera move)
  *   rt_accum_holes, rt_accum_fill: no counterpart either (after a reprojection, samples only for the pixels that
@@ -55,7 +58,8 @@ extern "C" {
                              rt_accum_counts, rt_accum_select*) and the views and reprojection (rt_scene_view,
                              rt_scene_get_view, rt_accum_reproject) and the hole fill (rt_accum_holes*,
                              rt_accum_fill) and the pixel-list kernel families (rt_render_pixels_path,
-                             rt_render_pixels_with*, RT_LIST_*) */
+                             rt_render_pixels_with*, RT_LIST_*) and the batched passes with their families
+                             (rt_render_pixel_passes*, rt_accum_plan*, rt_accum_add_passes, rt_accum_refine) */
 
 /* return codes */
 #define RT_OK 0
@@ -462,7 +466,9 @@ int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* pa
  * rgb_out[off[e] + i] its RGB8. params->seed is ignored. params, flags and the list: rt_render_pixels' rules
  * (RT_FLAG_MIS passes through; RT_FLAG_FP32 and RT_FLAG_MESH_NEAREST are RT_E_INVAL); in addition width * height must
  * be below 2^28 and the unit total sum(counts) at most width * height (RT_E_INVAL, before any device call). The
- * fused megakernel's body runs it for every scene (k_render_passes_f64; the pool kernels have no such instance).
+ * family rule is the pixel list's: the fused megakernel's body runs it (k_render_passes_f64), or, for a mesh scene
+ * whose full frame runs a pool kernel, that kernel's passes instance; rt_render_pixels_path answers for
+ * a batched render too, and the bits are the same whichever runs.
  * n_pixels = 0 returns RT_OK without a launch. cancel and stats as in rt_render;
  * stats->samples = units * 4 * floor(spp / 4). Every argument check runs without a GPU. */
 int rt_render_pixel_passes(const rt_scene* scene, const rt_render_params* params, const uint32_t* pixels,
@@ -477,6 +483,19 @@ int rt_render_pixel_passes(const rt_scene* scene, const rt_render_params* params
 int rt_render_pixel_passes_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
                                   const void* d_counts, int64_t n_pixels, int64_t units, const uint64_t* seeds,
                                   int32_t n_seeds, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats);
+/* rt_render_pixel_passes with the family chosen by the caller, by rt_render_pixels_with's rules: RT_LIST_AUTO is
+ * rt_render_pixel_passes (the scene's pool wherever it has one); an unknown family, or one the scene has no instance
+ * of (rt_render_pixels_path's path_out[1] names the one it has), is RT_E_INVAL before any device call. Same bits
+ * whichever family runs. rt_accum_add_passes and rt_accum_refine follow RT_LIST_AUTO. */
+int rt_render_pixel_passes_with(const rt_scene* scene, const rt_render_params* params, const uint32_t* pixels,
+                                const uint8_t* counts, int64_t n_pixels, const uint64_t* seeds /* host */,
+                                int32_t n_seeds, int32_t path, uint8_t* rgb_out, double* sub_out,
+                                const volatile int32_t* cancel, rt_render_stats* stats);
+/* rt_render_pixel_passes_device with the family chosen by the caller, by the same rules. */
+int rt_render_pixel_passes_with_device(const rt_scene* scene, const rt_render_params* params, const void* d_pixels,
+                                       const void* d_counts, int64_t n_pixels, int64_t units, const uint64_t* seeds,
+                                       int32_t n_seeds, int32_t path, void* d_rgb, void* d_sub, void* stream,
+                                       rt_render_stats* stats);
 /* rt_accum_select plus a pass count per listed pixel: how many passes of n samples per subpixel the pixel should get
  * at once. n >= 1, gain in (0, 1] (the share of the predicted need to hand out), max_passes = C in 1 .. RT_PASSES_MAX,
  * tolerances and K as rt_accum_select, width * height < 2^28; RT_E_INVAL otherwise, before any device call. For a pixel

@@ -85,12 +85,28 @@ RT_DEV SubPixel subpixel_of_pixel(const RenderArgs& a, uint32_t p, int u) {
     s.sy = s.sub >> 1;
     return s;
 }
-// The one place a pool kernel's unit id becomes a pixel: the frame instances (L = false) map the tile-local id,
-// the list instances (L = true) read the list (id < 4 n_pixels for every unit a ticket hands out).
-template <bool L>
+// What a unit list holds, for the fused body and the two pool bodies alike: nothing (kFrame: units are the tile's
+// subpixels), a frame pixel per unit-group (kList), or a (pixel, pass) word per unit-group
+// (kPasses): pixel | pass << kPassShift, the pass indexing a table of 16 seeds on the device.
+constexpr int kFrame = 0, kList = 1, kPasses = 2;
+constexpr int kPassShift = 28;
+constexpr uint32_t kPassPixMask = (1u << kPassShift) - 1u;
+// The one place a pool kernel's unit id becomes a pixel: the frame instances (L = kFrame) map the tile-local id,
+// the list instances (kList) read the list, the passes instances (kPasses) mask the pixel out of the unit word
+// (id < 4 n_pixels, or 4 n_units, for every unit a ticket hands out).
+template <int L>
 RT_DEV SubPixel unit_subpixel(const RenderArgs& a, const uint32_t* pixels, int id) {
-    if constexpr (L) return subpixel_of_pixel(a, pixels[id >> 2], id);
+    if constexpr (L == kPasses) return subpixel_of_pixel(a, pixels[id >> 2] & kPassPixMask, id);
+    else if constexpr (L == kList) return subpixel_of_pixel(a, pixels[id >> 2], id);
     else return subpixel_of(a, id);
+}
+// ... and the one place it becomes a seed: the launch's (frame and list instances: a.seed, no load), or in a passes
+// instance the seed of the unit word's pass (the word is unit_subpixel's load; the seed depends on it: two dependent
+// loads per camera sample).
+template <int L>
+RT_DEV uint64_t unit_seed(const RenderArgs& a, const uint32_t* units, const uint64_t* seeds, int id) {
+    if constexpr (L == kPasses) return seeds[units[id >> 2] >> kPassShift];
+    else return a.seed;
 }
 
 // Camera ray of sample `smp` of subpixel `sp` (server.rs:338-357): its direction and the sample's
@@ -126,9 +142,10 @@ RT_DEV void begin_path(const DevScene& sc, const CameraSample& cs, PathState& ps
     ps.depth = 0;
     ps.kind = K_CAMERA;
 }
-// New camera path for sample `smp` of subpixel `sp` (server.rs:338-357).
-RT_DEV void begin_sample(const DevScene& sc, const RenderArgs& a, const SubPixel& sp, int smp, PathState& ps) {
-    Rng rng(a.seed, sp.pid, (uint32_t)smp, (uint32_t)sp.sub);
+// New camera path for sample `smp` of subpixel `sp` (server.rs:338-357), drawn from `seed`.
+RT_DEV void begin_sample_seeded(const DevScene& sc, const RenderArgs& a, const SubPixel& sp, int smp, PathState& ps,
+                                uint64_t seed) {
+    Rng rng(seed, sp.pid, (uint32_t)smp, (uint32_t)sp.sub);
     double u1 = rng.uniform(), u2 = rng.uniform();
     ps.r0 = rng.s0;
     ps.r1 = rng.s1;
@@ -140,6 +157,10 @@ RT_DEV void begin_sample(const DevScene& sc, const RenderArgs& a, const SubPixel
     ps.pdf_prev = 0.0;
     ps.depth = 0;
     ps.kind = K_CAMERA;
+}
+// (seed: a.seed for a frame or a pixel list; the unit's own pass seed in a batched render)
+RT_DEV void begin_sample(const DevScene& sc, const RenderArgs& a, const SubPixel& sp, int smp, PathState& ps) {
+    begin_sample_seeded(sc, a, sp, smp, ps, a.seed);
 }
 
 // A shadow ray whose mesh test is deferred to the wavefront's k_wf_shadow_mesh (the analytic

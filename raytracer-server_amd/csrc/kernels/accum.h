@@ -40,7 +40,7 @@ hipError_t launch_accum_holes(const uint32_t* cnt, int width, int height, int32_
                               uint32_t* out, long cap, uint32_t* total, unsigned long long* n_holes, hipStream_t st);
 
 // Batched passes (rt_ffi.h rt_accum_plan). The most passes one entry may hold: the pass index rides in
-// the top 4 bits of a unit word (render_f64.hip kPassShift).
+// the top 4 bits of a unit word (integrator_f64.h kPassShift).
 constexpr int kPassesMax = 16;
 // The plan's first two passes: the selection's ballots and scanned block offsets in `scratch` (as launch_accum_select
 // leaves them), want[pix] = the pass count each active pixel wants before the frame cap (0: inactive),

@@ -96,11 +96,20 @@ inline int list_pool_family(const RenderArgs& a, bool slot_tables) {
 hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
                                   double* sub_buf, uint32_t* next_unit, int family, double* tail_buf, size_t tail_cap,
                                   hipStream_t st);
-// Batched passes (render_f64.hip k_render_passes_f64): unit-group u renders frame pixel
-// units[u] & (2^28 - 1) with the seed seeds[units[u] >> 28] (device: n_units words, 16 seeds) into sub_buf[u][4][3];
-// width * height < 2^28 and n_units * 4 <= INT32_MAX (hipErrorInvalidValue otherwise). The fused family only.
+// Batched passes (render_f64.hip): unit-group u renders frame pixel units[u] & (2^28 - 1) with the
+// seed seeds[units[u] >> 28] (device: n_units words, 16 seeds) into sub_buf[u][4][3]; width * height < 2^28 and
+// n_units * 4 <= INT32_MAX (hipErrorInvalidValue otherwise). family, tail_buf, tail_cap: as launch_render_list_f64's
+// (kListFused: k_render_passes_f64; kListFpool / kListRoles: the passes instances of the scene's pool kernel,
+// launch_render_passes_flat_f64 / launch_render_passes_roles_f64, which must be list_pool_family's answer).
 hipError_t launch_render_passes_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* units, long n_units,
-                                    const uint64_t* seeds, double* sub_buf, uint32_t* next_unit, hipStream_t st);
+                                    const uint64_t* seeds, double* sub_buf, uint32_t* next_unit, int family,
+                                    double* tail_buf, size_t tail_cap, hipStream_t st);
+hipError_t launch_render_passes_flat_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* units, long n_units,
+                                         const uint64_t* seeds, double* sub_buf, uint32_t* next_sub, double* tail_buf,
+                                         size_t tail_cap, hipStream_t st);
+hipError_t launch_render_passes_roles_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* units, long n_units,
+                                          const uint64_t* seeds, double* sub_buf, uint32_t* next_sub, double* tail_buf,
+                                          size_t tail_cap, hipStream_t st);
 hipError_t launch_render_list_flat_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
                                        double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
                                        hipStream_t st);

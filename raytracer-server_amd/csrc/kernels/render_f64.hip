@@ -5,7 +5,9 @@
 //                       whose frame kernel has no list instance (Phong mesh scenes, octrees without slot tables) or
 //                       whose list is short; launch_render_list_f64 hands the other mesh scenes' lists to the list
 //                       instances of the frame's own pool kernels, which give the same bits.
-//   k_render_passes_f64 — the same loop over a list of (pixel, pass) units with a seed per pass.
+//   k_render_passes_f64 — the same loop over a list of (pixel, pass) units with a seed per pass;
+//                       launch_render_passes_f64 hands the scenes with pool list instances to the pools' passes
+//                       instances.
 //   k_trace_f64       — Scene::trace_ray for a batch of rays (parity tests of the intersectors).
 //   wavefront kernels — see wavefront_f64.hip.
 #include <hip/hip_runtime.h>
@@ -78,9 +80,7 @@ __device__ unsigned long long g_dbg_wave[kDbgWaveRec * kDbgWaves];
 // within one unit, so the seed is a per-unit fact as the pixel is; nothing else in the loop knows about passes. The
 // pass rides in the top 4 bits of the pixel's register (frames of width * height < 2^28: the host checks), so the
 // instance needs no register beyond the list's; the seed is an 8-byte load beside the camera sample's arithmetic.
-constexpr int kFrame = 0, kList = 1, kPasses = 2;
-constexpr int kPassShift = 28;
-constexpr uint32_t kPassPixMask = (1u << kPassShift) - 1u;
+// (kFrame / kList / kPasses, kPassShift and kPassPixMask: integrator_f64.h, shared with the pool bodies)
 template <int F, int L>
 __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
                                            uint32_t* next_sub, long nsub, int refill,
@@ -694,9 +694,10 @@ hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a_in, co
     return hipGetLastError();
 }
 
-// Batched passes: the fused body's kPasses instance of a.features & 15 over n_units (pixel, pass)
-// words; mesh instances at 3 waves/SIMD and analytic ones at RT_MK_W4, planned like a pixel list (plan_units, no
-// split tail). Only the fused family has this instance.
+// Batched passes. family kListFused: the fused body's kPasses instance of a.features & 15 over
+// n_units (pixel, pass) words; mesh instances at 3 waves/SIMD and analytic ones at RT_MK_W4, planned like a pixel list
+// (plan_units, no split tail). kListFpool / kListRoles: the passes instances of the scene's pool kernel, planned as
+// their list instances are (split tail included).
 template <int F>
 static void launch_mk_passes(const DevScene& sc, RenderArgs a, double* sub_buf, uint32_t* next_unit, int refill,
                              const uint32_t* units, const uint64_t* seeds, hipStream_t st) {
@@ -708,7 +709,8 @@ static void launch_mk_passes(const DevScene& sc, RenderArgs a, double* sub_buf, 
                        nsub, refill, units, seeds);
 }
 hipError_t launch_render_passes_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* units, long n_units,
-                                    const uint64_t* seeds, double* sub_buf, uint32_t* next_unit, hipStream_t st) {
+                                    const uint64_t* seeds, double* sub_buf, uint32_t* next_unit, int family,
+                                    double* tail_buf, size_t tail_cap, hipStream_t st) {
     if (n_units <= 0 || a_in.n_samples <= 0) return hipSuccess;
     if (n_units > 0x7fffffffL / 4 || (long)a_in.width * a_in.height > (long)kPassPixMask || !units || !seeds)
         return hipErrorInvalidValue;
@@ -720,6 +722,13 @@ hipError_t launch_render_passes_f64(const DevScene& sc, const RenderArgs& a_in, 
     t_tail_plan = TailPlan{};
     hipError_t e = hipMemsetAsync(next_unit, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
+    // a family the scene has no instance of is an error, never a quiet change of kernel (launch_render_list_f64's rule)
+    if (family != kListFused) {
+        if (family != list_pool_family(a, sc.node_slot != nullptr)) return hipErrorInvalidValue;
+        if (family == kListFpool)
+            return launch_render_passes_flat_f64(sc, a, units, n_units, seeds, sub_buf, next_unit, tail_buf, tail_cap, st);
+        return launch_render_passes_roles_f64(sc, a, units, n_units, seeds, sub_buf, next_unit, tail_buf, tail_cap, st);
+    }
     const int refill = cam_refill();
 #define RT_MP_CASE(F) case F: launch_mk_passes<F>(sc, a, sub_buf, next_unit, refill, units, seeds, st); break;
     switch (a.features & 15) {

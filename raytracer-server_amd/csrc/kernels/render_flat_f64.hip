@@ -547,13 +547,16 @@ __global__ __launch_bounds__(kBlk, W) void k_megakernel_flat_f64(DevScene sc_g, 
 #define RT_FPOOL_SINK 1  // A/B: shade_vertex writes the shadow query's ray into the LDS columns (LdsQuerySink)
 #endif
 
-// The kernel's body, shared by its frame instances (L = false: k_megakernel_fpool_f64, units are the tile's
-// subpixels) and its pixel-list instances (L = true: k_megakernel_fpool_list_f64, unit 4 e + j is subpixel j of the
-// frame pixel pixels[e]). Everything but unit_subpixel works on the compact unit id.
-template <int F, int B, bool L>
+// The kernel's body, shared by its frame instances (L = kFrame: k_megakernel_fpool_f64, units are the tile's
+// subpixels), its pixel-list instances (L = kList: k_megakernel_fpool_list_f64, unit 4 e + j is subpixel j of the
+// frame pixel pixels[e]) and its batched-passes instances (L = kPasses: k_megakernel_fpool_passes_f64,
+// unit 4 u + j is subpixel j of the frame pixel in the word pixels[u], drawn from seeds[the word's pass]; DESIGN.md
+// §18). Everything but unit_subpixel and unit_seed, at the two camera samples, works on the compact unit id.
+template <int F, int B, int L>
 __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
                                            uint32_t* next_sub, long nsub, int pool_min, int refill,
-                                           const uint32_t* __restrict__ pixels) {
+                                           const uint32_t* __restrict__ pixels,
+                                           const uint64_t* __restrict__ seeds = nullptr) {
     using C = Cfg<F | kCfgLdsObj>;  // the object table in LDS (path_f64.h rt_lds_objects)
     static_assert(C::mesh && C::compact && !C::bvh, "flat-mesh kernel: compact scenes, octree meshes");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves (path_f64.h: the diagnostic builds' per-wave LDS)");
@@ -809,7 +812,8 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
             const bool need = active && !fresh && !nvalid && unit_has_next(a, id, s);
             if (refill > 0 && __popcll(__ballot(need)) >= refill) {
                 if (need) {
-                    const CameraSample nb = camera_sample(sc, a, unit_subpixel<L>(a, pixels, id), s + 1);
+                    const CameraSample nb = camera_sample_seeded(sc, a, unit_subpixel<L>(a, pixels, id), s + 1,
+                                                                 unit_seed<L>(a, pixels, seeds, id));
                     nbd[0] = nb.d.x; nbd[B] = nb.d.y; nbd[2 * B] = nb.d.z;
                     nbr[0] = nb.r0; nbr[B] = nb.r1;
                     nvalid = true;
@@ -822,7 +826,7 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
         if (tr) {
             if (fresh) {
                 if (C::nospec && nvalid) begin_path(sc, CameraSample{v3(nbd[0], nbd[B], nbd[2 * B]), nbr[0], nbr[B]}, ps);
-                else begin_sample(sc, a, unit_subpixel<L>(a, pixels, id), s, ps);
+                else begin_sample_seeded(sc, a, unit_subpixel<L>(a, pixels, id), s, ps, unit_seed<L>(a, pixels, seeds, id));
                 nvalid = false;
                 fresh = false;
             }
@@ -862,7 +866,7 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
 template <int F, int W, int B = kBlk>
 __global__ __launch_bounds__(B, W) void k_megakernel_fpool_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                                  uint32_t* next_sub, long nsub, int pool_min, int refill) {
-    fpool_body<F, B, false>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, nullptr);
+    fpool_body<F, B, kFrame>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, nullptr);
 }
 // The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
 template <int F, int W, int B = kBlk>
@@ -870,20 +874,34 @@ __global__ __launch_bounds__(B, W) void k_megakernel_fpool_list_f64(DevScene sc_
                                                                       double* __restrict__ sub_buf, uint32_t* next_sub,
                                                                       long nsub, int pool_min, int refill,
                                                                       const uint32_t* __restrict__ pixels) {
-    fpool_body<F, B, true>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, pixels);
+    fpool_body<F, B, kList>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, pixels);
+}
+// The batched-passes instance: nsub = 4 n_units units, units[u] = pixel | pass << 28 (pass < 16),
+// seeds[16] on the device, sub_buf the compact [n_units][4][3] buffer. Scheduling is the list instance's.
+template <int F, int W, int B = kBlk>
+__global__ __launch_bounds__(B, W) void k_megakernel_fpool_passes_f64(DevScene sc_g, RenderArgs a_g,
+                                                                        double* __restrict__ sub_buf, uint32_t* next_sub,
+                                                                        long nsub, int pool_min, int refill,
+                                                                        const uint32_t* __restrict__ units,
+                                                                        const uint64_t* __restrict__ seeds) {
+    fpool_body<F, B, kPasses>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, units, seeds);
 }
 
-// One launch of the query pool, with its split tail planned: a frame (L = false) or a pixel list (L = true: nsub =
-// 4 n_pixels compact units).
-template <int F, int W, int B, bool L>
+// One launch of the query pool, with its split tail planned: a frame (L = kFrame), a pixel list (kList: nsub =
+// 4 n_pixels compact units) or a list of (pixel, pass) words with their seeds (kPasses: nsub = 4 n_units).
+template <int F, int W, int B, int L>
 static void launch_fpool(const DevScene& sc, RenderArgs& a, double* sub_buf, uint32_t* next_sub, long nsub,
                          double* tail_buf, size_t tail_cap, int pool_min, int refill, const uint32_t* pixels,
-                         hipStream_t st) {
+                         const uint64_t* seeds, hipStream_t st) {
     long blocks;
-    if constexpr (L) blocks = resident_blocks(k_megakernel_fpool_list_f64<F, W, B>, (nsub + B - 1) / B, B);
+    if constexpr (L == kPasses) blocks = resident_blocks(k_megakernel_fpool_passes_f64<F, W, B>, (nsub + B - 1) / B, B);
+    else if constexpr (L == kList) blocks = resident_blocks(k_megakernel_fpool_list_f64<F, W, B>, (nsub + B - 1) / B, B);
     else blocks = resident_blocks(k_megakernel_fpool_f64<F, W, B>, (nsub + B - 1) / B, B);
     plan_tail(a, nsub, blocks * B, tail_buf, tail_cap, tail_split_x2(nsub, blocks * B));
-    if constexpr (L)
+    if constexpr (L == kPasses)
+        hipLaunchKernelGGL((k_megakernel_fpool_passes_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
+                           next_sub, nsub, pool_min, refill, pixels, seeds);
+    else if constexpr (L == kList)
         hipLaunchKernelGGL((k_megakernel_fpool_list_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
                            next_sub, nsub, pool_min, refill, pixels);
     else
@@ -919,15 +937,17 @@ static bool fpool_nospec(const RenderArgs& a) {
     return nospec && (a.features & 32) && !(a.features & 2);
 }
 
-// The product dispatch of the query pool, for a frame or a pixel list: F | 32 at RT_FPOOL_BLOCK for scenes without a
-// mirror or Phong object, F at 3 waves/SIMD otherwise, then the split tail's sum. Lists have no Phong instances.
-template <bool L>
+// The product dispatch of the query pool, for a frame, a pixel list or a list of passes: F | 32 at RT_FPOOL_BLOCK for
+// scenes without a mirror or Phong object, F at 3 waves/SIMD otherwise, then the split tail's sum. Lists and passes
+// have no Phong instances.
+template <int L>
 static hipError_t launch_fpool_product(const DevScene& sc, RenderArgs& a, double* sub_buf, uint32_t* next_sub, long nsub,
-                                       double* tail_buf, size_t tail_cap, const uint32_t* pixels, hipStream_t st) {
-    if (L && (a.features & 2)) return hipErrorInvalidValue;  // Phong scenes stay on k_render_list_f64
+                                       double* tail_buf, size_t tail_cap, const uint32_t* pixels, const uint64_t* seeds,
+                                       hipStream_t st) {
+    if (L != kFrame && (a.features & 2)) return hipErrorInvalidValue;  // Phong scenes stay on the fused body's instances
 #define RT_FPOOL_CASE(F, W, B, LL)                                                                                        \
     case (F) & 15:                                                                                                        \
-        launch_fpool<F, W, B, LL>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), pixels, st); \
+        launch_fpool<F, W, B, LL>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), pixels, seeds, st); \
         break;
     if (fpool_nospec(a)) {
         switch (a.features & 15) {
@@ -938,7 +958,7 @@ static hipError_t launch_fpool_product(const DevScene& sc, RenderArgs& a, double
     } else {
         switch (a.features & 15) {
             RT_FPOOL_CASE(9, 3, kBlk, L) RT_FPOOL_CASE(13, 3, kBlk, L)
-            RT_FPOOL_CASE(11, 3, kBlk, false) RT_FPOOL_CASE(15, 3, kBlk, false)  // Phong: frames only (lists returned above)
+            RT_FPOOL_CASE(11, 3, kBlk, kFrame) RT_FPOOL_CASE(15, 3, kBlk, kFrame)  // Phong: frames only (lists returned above)
             default: return hipErrorInvalidValue;
         }
     }
@@ -962,7 +982,7 @@ hipError_t launch_megakernel_flat_f64(const DevScene& sc, const RenderArgs& a_in
     if (!fpool || (waves == 2 && !fpool_nospec(a))) {
 #define RT_FLAT_CASE(F)                                                                                                   \
     case F:                                                                                                               \
-        if (fpool) launch_fpool<F, 2, kBlk, false>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), nullptr, st); \
+        if (fpool) launch_fpool<F, 2, kBlk, kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), nullptr, nullptr, st); \
         else if (waves == 2) launch_flat<F, 2>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st);                   \
         else launch_flat<F, 3>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st);                                   \
         break;
@@ -975,7 +995,7 @@ hipError_t launch_megakernel_flat_f64(const DevScene& sc, const RenderArgs& a_in
         return hipGetLastError();
     }
 #endif
-    return launch_fpool_product<false>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, st);
+    return launch_fpool_product<kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, nullptr, st);
 }
 
 // The query pool over a pixel list (kernels.h list_pool_family == kListFpool: flat octrees, no Phong
@@ -985,7 +1005,16 @@ hipError_t launch_render_list_flat_f64(const DevScene& sc, const RenderArgs& a_i
                                        double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
                                        hipStream_t st) {
     RenderArgs a = a_in;
-    return launch_fpool_product<true>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, st);
+    return launch_fpool_product<kList>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, nullptr, st);
+}
+
+// The query pool over a list of (pixel, pass) words: the list launcher with the passes instances,
+// nsub = 4 n_units compact units. Called by launch_render_passes_f64 after the ticket counter is reset.
+hipError_t launch_render_passes_flat_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* units, long n_units,
+                                         const uint64_t* seeds, double* sub_buf, uint32_t* next_sub, double* tail_buf,
+                                         size_t tail_cap, hipStream_t st) {
+    RenderArgs a = a_in;
+    return launch_fpool_product<kPasses>(sc, a, sub_buf, next_sub, n_units * 4, tail_buf, tail_cap, units, seeds, st);
 }
 
 // rt_diag_trace / rt_diag_visible, the flat query pool's split of a query (RenderArgs::all_flat scenes): the

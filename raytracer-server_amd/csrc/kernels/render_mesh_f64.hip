@@ -949,12 +949,15 @@ RT_DEV void role_query_closest(const RP& P, int p, const HitRec& h, uint32_t nea
     P.I(RI_NEAR, p) = (int32_t)near;
 }
 
-// The kernel's body, shared by its frame instances (L = false: k_megakernel_roles_f64, units are the tile's
-// subpixels) and its pixel-list instances (L = true: k_megakernel_roles_list_f64, unit 4 e + j is subpixel j of the
-// frame pixel pixels[e]). Everything but unit_subpixel works on the compact unit id.
-template <int F, bool S, int B, bool L>
+// The kernel's body, shared by its frame instances (L = kFrame: k_megakernel_roles_f64, units are the tile's
+// subpixels), its pixel-list instances (L = kList: k_megakernel_roles_list_f64, unit 4 e + j is subpixel j of the
+// frame pixel pixels[e]) and its batched-passes instances (L = kPasses: k_megakernel_roles_passes_f64,
+// unit 4 u + j is subpixel j of the frame pixel in the word pixels[u], drawn from seeds[the word's pass]; DESIGN.md
+// §18). Everything but unit_subpixel and unit_seed, at the one camera sample, works on the compact unit id.
+template <int F, bool S, int B, int L>
 __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
-                                           uint32_t* next_sub, long nsub, const uint32_t* __restrict__ pixels) {
+                                           uint32_t* next_sub, long nsub, const uint32_t* __restrict__ pixels,
+                                           const uint64_t* __restrict__ seeds = nullptr) {
     using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0)>;
     static_assert(C::mesh && C::compact && !C::bvh, "the role-split pool walks octrees");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves, at most 16 (path_f64.h: the diagnostic builds' per-wave LDS)");
@@ -1210,7 +1213,8 @@ __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArg
             if (retire) p = -1;
             // the next ray: the path going on, or its unit's next sample
             if (p >= 0 && !park && (rs == RS_TRACE || rs == RS_FRESH)) {
-                if (rs == RS_FRESH) begin_sample(sc, a, unit_subpixel<L>(a, pixels, id), s, ps);
+                if (rs == RS_FRESH)
+                    begin_sample_seeded(sc, a, unit_subpixel<L>(a, pixels, id), s, ps, unit_seed<L>(a, pixels, seeds, id));
                 RT_DBG_TSTART(t_ta);
                 const RayInv wi = make_inv(ps.ray.d);
                 const HitRec h = trace_analytic<C>(sc, ps.ray, wi);
@@ -1239,30 +1243,43 @@ __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArg
 template <int F, int W, bool S, int B = RoleShape<Cfg<F>>::block>
 __global__ __launch_bounds__(B, W) void k_megakernel_roles_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                                 uint32_t* next_sub, long nsub) {
-    roles_body<F, S, B, false>(sc_g, a_g, sub_buf, next_sub, nsub, nullptr);
+    roles_body<F, S, B, kFrame>(sc_g, a_g, sub_buf, next_sub, nsub, nullptr);
 }
 // The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
 template <int F, int W, bool S, int B = RoleShape<Cfg<F>>::block>
 __global__ __launch_bounds__(B, W) void k_megakernel_roles_list_f64(DevScene sc_g, RenderArgs a_g,
                                                                      double* __restrict__ sub_buf, uint32_t* next_sub,
                                                                      long nsub, const uint32_t* __restrict__ pixels) {
-    roles_body<F, S, B, true>(sc_g, a_g, sub_buf, next_sub, nsub, pixels);
+    roles_body<F, S, B, kList>(sc_g, a_g, sub_buf, next_sub, nsub, pixels);
+}
+// The batched-passes instance: nsub = 4 n_units units, units[u] = pixel | pass << 28 (pass < 16),
+// seeds[16] on the device, sub_buf the compact [n_units][4][3] buffer. Scheduling is the list instance's.
+template <int F, int W, bool S, int B = RoleShape<Cfg<F>>::block>
+__global__ __launch_bounds__(B, W) void k_megakernel_roles_passes_f64(DevScene sc_g, RenderArgs a_g,
+                                                                       double* __restrict__ sub_buf, uint32_t* next_sub,
+                                                                       long nsub, const uint32_t* __restrict__ units,
+                                                                       const uint64_t* __restrict__ seeds) {
+    roles_body<F, S, B, kPasses>(sc_g, a_g, sub_buf, next_sub, nsub, units, seeds);
 }
 
-// One launch of the role-split pool, its split tail planned and summed: a frame (L = false) or a pixel list (L = true:
-// nsub = 4 n_pixels compact units).
-template <int F, bool L, bool S = (RT_WALK_TIGHT != 0)>
+// One launch of the role-split pool, its split tail planned and summed: a frame (L = kFrame), a pixel list (kList:
+// nsub = 4 n_pixels compact units) or a list of (pixel, pass) words with their seeds (kPasses: nsub = 4 n_units).
+template <int F, int L, bool S = (RT_WALK_TIGHT != 0)>
 static void launch_roles(const DevScene& sc, const RenderArgs& a_in, double* sub_buf, uint32_t* next_sub, long nsub,
-                         double* tail_buf, size_t tail_cap, const uint32_t* pixels, hipStream_t st) {
+                         double* tail_buf, size_t tail_cap, const uint32_t* pixels, const uint64_t* seeds, hipStream_t st) {
     constexpr int B = RoleShape<Cfg<F>>::block, W = B / 256;  // one block per CU: B / 256 waves per SIMD
     long blocks;
-    if constexpr (L) blocks = resident_blocks(k_megakernel_roles_list_f64<F, W, S>, (nsub + B - 1) / B, B);
+    if constexpr (L == kPasses) blocks = resident_blocks(k_megakernel_roles_passes_f64<F, W, S>, (nsub + B - 1) / B, B);
+    else if constexpr (L == kList) blocks = resident_blocks(k_megakernel_roles_list_f64<F, W, S>, (nsub + B - 1) / B, B);
     else blocks = resident_blocks(k_megakernel_roles_f64<F, W, S>, (nsub + B - 1) / B, B);
     RenderArgs a = a_in;
     // the split tail and ticket runs planned for the lanes that hold paths (one path slot per thread)
     // six subpixels per path slot; runs of whole subpixels of ~64 samples (plan_units)
     plan_tail(a, nsub, blocks * RoleLayout<Cfg<F>>::paths, tail_buf, tail_cap, 12, 1, 64);
-    if constexpr (L)
+    if constexpr (L == kPasses)
+        hipLaunchKernelGGL((k_megakernel_roles_passes_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
+                           next_sub, nsub, pixels, seeds);
+    else if constexpr (L == kList)
         hipLaunchKernelGGL((k_megakernel_roles_list_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
                            next_sub, nsub, pixels);
     else
@@ -1312,7 +1329,7 @@ hipError_t launch_megakernel_mesh_f64(const DevScene& sc, const RenderArgs& a, d
     case F:                                                                                    \
         if (!sc.node_slot) launch_mm<F, 2, 1, false>(sc, a, sub_buf, next_sub, nsub, pool_ksteps, wmin, pool_refill, pool_min, pool_vmin, tail_buf, tail_cap, st); \
         RT_MM_AB(F)                                                                            \
-        else launch_roles<F, false>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, st); \
+        else launch_roles<F, kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, nullptr, st); \
         break;
 #define RT_MMB_CASE(F)                                                                         \
     case F:                                                                                    \
@@ -1337,8 +1354,22 @@ hipError_t launch_render_list_roles_f64(const DevScene& sc, const RenderArgs& a,
                                         hipStream_t st) {
     if (!sc.node_slot) return hipErrorInvalidValue;  // octrees without slot tables stay on k_render_list_f64
     switch (a.features & 31) {
-        case 9: launch_roles<9, true>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, st); break;
-        case 13: launch_roles<13, true>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, st); break;
+        case 9: launch_roles<9, kList>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, nullptr, st); break;
+        case 13: launch_roles<13, kList>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, nullptr, st); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// The role-split pool over a list of (pixel, pass) words: the list launcher with the passes
+// instances, nsub = 4 n_units compact units. Called by launch_render_passes_f64 after the ticket counter is reset.
+hipError_t launch_render_passes_roles_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* units, long n_units,
+                                          const uint64_t* seeds, double* sub_buf, uint32_t* next_sub, double* tail_buf,
+                                          size_t tail_cap, hipStream_t st) {
+    if (!sc.node_slot) return hipErrorInvalidValue;  // octrees without slot tables stay on k_render_passes_f64
+    switch (a.features & 31) {
+        case 9: launch_roles<9, kPasses>(sc, a, sub_buf, next_sub, n_units * 4, tail_buf, tail_cap, units, seeds, st); break;
+        case 13: launch_roles<13, kPasses>(sc, a, sub_buf, next_sub, n_units * 4, tail_buf, tail_cap, units, seeds, st); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

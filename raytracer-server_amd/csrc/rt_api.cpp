@@ -2649,7 +2649,7 @@ int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* p,
 namespace {
 
 static_assert(RT_PASSES_MAX == rt::kPassesMax, "accum.h mirrors rt_ffi.h's RT_PASSES_MAX");
-// a unit word holds the pixel id below the pass index (render_f64.hip kPassShift)
+// a unit word holds the pixel id below the pass index (integrator_f64.h kPassShift)
 constexpr int64_t kPassFramePixels = (int64_t)1 << 28;
 
 // The accumulator's batch buffers: want | counts | off | units | expansion scratch | words | seeds.
@@ -2718,14 +2718,18 @@ hipError_t seeds_upload(uint64_t* d_seeds, const uint64_t* seeds, int32_t n_seed
     return hipMemcpyAsync(d_seeds, h16, RT_PASSES_MAX * sizeof(uint64_t), hipMemcpyHostToDevice, st);
 }
 
-// render_pixels_enqueue for unit words (k_render_passes_f64 + k_finalize_f64 on the compact buffer): n_units > 0
-// device words and 16 device seeds; arguments checked by check_passes. d_rgb and d_sub may be null.
+// render_pixels_enqueue for unit words (the passes kernel of `path`'s family + k_finalize_f64 on the compact buffer):
+// n_units > 0 device words and 16 device seeds; arguments checked by check_passes (and list_family_of for a path other
+// than RT_LIST_AUTO: the family rule is the pixel list's). d_rgb and d_sub may be null.
 int render_passes_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t* d_units, int64_t n_units,
                           const uint64_t* d_seeds, uint8_t* d_rgb, double* d_sub, hipStream_t st, const int32_t* dcancel,
-                          PendingStats* ps) {
+                          PendingStats* ps, int32_t path = RT_LIST_AUTO) {
+    int family = RT_LIST_FUSED;
+    int rc = list_family_of("batched render", s, p, n_units, path, &family);
+    if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     rt::DevScene ds;
-    int rc = upload(s, p->device, &ds);
+    rc = upload(s, p->device, &ds);
     if (rc != RT_OK) return rc;
     rt::RenderArgs a = make_render_args(s, p, ds);
     a.x0 = 0;
@@ -2756,7 +2760,10 @@ int render_passes_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t
     if (e == hipSuccess && a.n_samples <= 0) e = hipMemsetAsync(sub, 0, (size_t)n_units * 12 * sizeof(double), st);
     if (e == hipSuccess) {
         a.counters = ps ? ws->counters : nullptr;
-        e = rt::launch_render_passes_f64(ds, a, d_units, (long)n_units, d_seeds, sub, (uint32_t*)(ws->counters + 4), st);
+        // the pool kernels split their last units into chunks of samples: the frame's scratch rule, for this many units
+        if (family != RT_LIST_FUSED) ensure_tail_scratch(ws.get(), a, (size_t)n_units);
+        e = rt::launch_render_passes_f64(ds, a, d_units, (long)n_units, d_seeds, sub, (uint32_t*)(ws->counters + 4), family,
+                                         ws->tail_buf, ws->tail_cap, st);
     }
     if (e == hipSuccess && d_rgb) e = rt::launch_finalize_f64(a, sub, st);
     if (e == hipSuccess && ps) e = hipEventRecord(ps->e1, st);
@@ -2845,6 +2852,7 @@ int batch_render_merge(const char* who, rt_accum* a, const rt_scene* scene, cons
     const hipError_t e = rt::launch_accum_expand(adapt_list(a), batch_counts(a), (long)n_pixels, batch_runs(a), batch_off(a),
                                                  batch_units(a), (long)units, batch_words(a) + 20, st);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    // RT_LIST_AUTO: the scene's pool wherever it has one
     int rc = render_passes_enqueue(const_cast<rt_scene*>(scene), p, batch_units(a), units, batch_seeds(a), nullptr,
                                    a->stage_sub(), st, call.mirror.dev, &call.ps);
     rc = call.finish(who, rc);
@@ -2854,14 +2862,16 @@ int batch_render_merge(const char* who, rt_accum* a, const rt_scene* scene, cons
 
 }  // namespace
 
-int rt_render_pixel_passes(const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels, const uint8_t* counts,
-                           int64_t n_pixels, const uint64_t* seeds, int32_t n_seeds, uint8_t* rgb_out, double* sub_out,
-                           const volatile int32_t* cancel, rt_render_stats* stats) {
+int rt_render_pixel_passes_with(const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels,
+                                const uint8_t* counts, int64_t n_pixels, const uint64_t* seeds, int32_t n_seeds, int32_t path,
+                                uint8_t* rgb_out, double* sub_out, const volatile int32_t* cancel, rt_render_stats* stats) {
     const char* who = "rt_render_pixel_passes";
     int rc = check_passes(who, scene, p, pixels, counts, n_pixels, seeds, n_seeds);
     if (rc == RT_OK) rc = check_pixel_list(who, pixels, n_pixels, (int64_t)p->width * p->height);
     int64_t units = 0;
     if (rc == RT_OK) rc = check_pass_counts(who, counts, n_pixels, n_seeds, (int64_t)p->width * p->height, &units);
+    int family;
+    if (rc == RT_OK) rc = list_family_of(who, scene, p, units, path, &family);
     if (rc != RT_OK) return rc;
     if (n_pixels == 0) {
         if (stats) std::memset(stats, 0, sizeof *stats);
@@ -2892,17 +2902,27 @@ int rt_render_pixel_passes(const rt_scene* scene, const rt_render_params* p, con
     if (e == hipSuccess) e = seeds_upload(d_seeds, seeds, n_seeds, h_seeds, call.cs.st);
     if (e != hipSuccess) return oom_or_hip(e, who);
     rc = render_passes_enqueue(const_cast<rt_scene*>(scene), p, d_units, units, d_seeds, rgb_out ? d_rgb : nullptr, d_sub,
-                               call.cs.st, call.mirror.dev, &call.ps);
+                               call.cs.st, call.mirror.dev, &call.ps, path);
     return call.finish(who, rc, {{rgb_out, d_rgb, n * 3}, {sub_out, d_sub, b_sub}});
 }
 
-int rt_render_pixel_passes_device(const rt_scene* scene, const rt_render_params* p, const void* d_pixels,
-                                  const void* d_counts, int64_t n_pixels, int64_t units, const uint64_t* seeds,
-                                  int32_t n_seeds, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats) {
+int rt_render_pixel_passes(const rt_scene* scene, const rt_render_params* p, const uint32_t* pixels, const uint8_t* counts,
+                           int64_t n_pixels, const uint64_t* seeds, int32_t n_seeds, uint8_t* rgb_out, double* sub_out,
+                           const volatile int32_t* cancel, rt_render_stats* stats) {
+    return rt_render_pixel_passes_with(scene, p, pixels, counts, n_pixels, seeds, n_seeds, RT_LIST_AUTO, rgb_out, sub_out,
+                                       cancel, stats);
+}
+
+int rt_render_pixel_passes_with_device(const rt_scene* scene, const rt_render_params* p, const void* d_pixels,
+                                       const void* d_counts, int64_t n_pixels, int64_t units, const uint64_t* seeds,
+                                       int32_t n_seeds, int32_t path, void* d_rgb, void* d_sub, void* stream,
+                                       rt_render_stats* stats) {
     const char* who = "rt_render_pixel_passes_device";
     int rc = check_passes(who, scene, p, d_pixels, d_counts, n_pixels, seeds, n_seeds);
     if (rc == RT_OK && (units < n_pixels || units > n_pixels * n_seeds || units > (int64_t)p->width * p->height))
         rc = fail(RT_E_INVAL, std::string(who) + ": units must be the sum of the counts, at most width * height");
+    int family;
+    if (rc == RT_OK) rc = list_family_of(who, scene, p, units, path, &family);
     if (rc != RT_OK) return rc;
     if (n_pixels == 0) {
         if (stats) std::memset(stats, 0, sizeof *stats);
@@ -2927,11 +2947,18 @@ int rt_render_pixel_passes_device(const rt_scene* scene, const rt_render_params*
     if (e != hipSuccess) rc = fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
     if (rc == RT_OK)
         rc = render_passes_enqueue(const_cast<rt_scene*>(scene), p, mem.at<uint32_t>(at_units), units, mem.at<uint64_t>(at_seeds),
-                                   (uint8_t*)d_rgb, (double*)d_sub, st, nullptr, stats ? &ps : nullptr);
+                                   (uint8_t*)d_rgb, (double*)d_sub, st, nullptr, stats ? &ps : nullptr, path);
     // the call's scratch lives until the render is done: this form always waits
     e = hipStreamSynchronize(st);
     if (rc == RT_OK && e != hipSuccess) rc = fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
     return stats_sync(rc, st, stats ? &ps : nullptr);
+}
+
+int rt_render_pixel_passes_device(const rt_scene* scene, const rt_render_params* p, const void* d_pixels,
+                                  const void* d_counts, int64_t n_pixels, int64_t units, const uint64_t* seeds,
+                                  int32_t n_seeds, void* d_rgb, void* d_sub, void* stream, rt_render_stats* stats) {
+    return rt_render_pixel_passes_with_device(scene, p, d_pixels, d_counts, n_pixels, units, seeds, n_seeds, RT_LIST_AUTO,
+                                              d_rgb, d_sub, stream, stats);
 }
 
 int rt_accum_plan_device(void* accum, float abs_tol, float rel_tol, int32_t max_n, int32_t n, float gain, int32_t max_passes,

@@ -101,7 +101,8 @@ _EXPORTS = ["rt_scene_load_toml", "rt_scene_create", "rt_scene_destroy", "rt_sce
             "rt_accum_select_device", "rt_scene_view", "rt_scene_get_view", "rt_accum_reproject", "rt_accum_holes",
             "rt_accum_holes_device", "rt_accum_fill", "rt_render_pixels_path", "rt_render_pixels_with",
             "rt_render_pixels_with_device", "rt_render_pixel_passes", "rt_render_pixel_passes_device", "rt_accum_plan",
-            "rt_accum_plan_device", "rt_accum_add_passes", "rt_accum_refine"]
+            "rt_accum_plan_device", "rt_accum_add_passes", "rt_accum_refine", "rt_render_pixel_passes_with",
+            "rt_render_pixel_passes_with_device"]
 
 
 def _load():
@@ -171,6 +172,10 @@ def _load():
                                          P(RenderStats)]
     L.rt_render_pixel_passes_device.argtypes = [vp, P(RenderParams), vp, vp, I64, I64, P(U64), I, vp, vp, vp,
                                                 P(RenderStats)]
+    L.rt_render_pixel_passes_with.argtypes = [vp, P(RenderParams), P(U32), P(U8), I64, P(U64), I, I, P(U8), P(D), P(I),
+                                              P(RenderStats)]
+    L.rt_render_pixel_passes_with_device.argtypes = [vp, P(RenderParams), vp, vp, I64, I64, P(U64), I, I, vp, vp, vp,
+                                                     P(RenderStats)]
     L.rt_accum_plan.argtypes = [vp, F, F, I, I, F, I, P(U32), P(U8), I64, P(I64), P(I64), P(I64)]
     L.rt_accum_plan_device.argtypes = [vp, F, F, I, I, F, I, vp, vp, I64, P(I64), P(I64), P(I64), vp]
     L.rt_accum_add_passes.argtypes = [vp, vp, P(RenderParams), P(U64), I, P(U32), P(U8), I64, P(I), P(RenderStats)]
@@ -751,12 +756,13 @@ def render_pixels(scene, width, height, pixels, spp, seed=0x5EED, mis=False, dev
 
 
 def render_pixel_passes(scene, width, height, pixels, counts, spp, seeds, mis=False, device=0, want_sub=False,
-                        want_rgb=True, cancel=None):
+                        want_rgb=True, cancel=None, path=LIST_AUTO):
     """render_pixels with counts[e] passes of pixel pixels[e] in one launch, pass i drawing from seeds[i]
-    (rt_render_pixel_passes; counts in 1 .. len(seeds) <= PASSES_MAX, at most width * height units in
-    all). Returns (rgb[units, 3] u8 or None, sub[units, 4, 3] f64 or None, stats), indexed by unit-group
+    (rt_render_pixel_passes_with; counts in 1 .. len(seeds) <= PASSES_MAX, at most width * height
+    units in all). Returns (rgb[units, 3] u8 or None, sub[units, 4, 3] f64 or None, stats), indexed by unit-group
     off[e] + i with off the exclusive prefix sum of counts; each is what render_pixels gives that pixel for
-    seeds[i], bit for bit."""
+    seeds[i], bit for bit. path: LIST_AUTO (the scene's pool kernel wherever it has one, see render_pixels_path) or the
+    kernel family to run; a family the scene has no instance of raises."""
     px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
     ct = np.ascontiguousarray(counts, dtype=np.uint8).reshape(-1)
     if ct.size != px.size:
@@ -767,10 +773,10 @@ def render_pixel_passes(scene, width, height, pixels, counts, spp, seeds, mis=Fa
     rgb = np.zeros((units, 3), dtype=np.uint8) if want_rgb else None
     sub = np.zeros((units, 4, 3), dtype=np.float64) if want_sub else None
     st = RenderStats()
-    rc = _check(lib.rt_render_pixel_passes(scene.handle, ctypes.byref(p), _ptr(px, ctypes.c_uint32),
-                                           _ptr(ct, ctypes.c_uint8), px.size, _ptr(sd, ctypes.c_uint64), sd.size,
-                                           _ptr(rgb, ctypes.c_uint8), _ptr(sub, ctypes.c_double),
-                                           ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st)))
+    rc = _check(lib.rt_render_pixel_passes_with(scene.handle, ctypes.byref(p), _ptr(px, ctypes.c_uint32),
+                                                _ptr(ct, ctypes.c_uint8), px.size, _ptr(sd, ctypes.c_uint64), sd.size,
+                                                path, _ptr(rgb, ctypes.c_uint8), _ptr(sub, ctypes.c_double),
+                                                ctypes.byref(cancel) if cancel is not None else None, ctypes.byref(st)))
     out = st.as_dict()
     out["cancelled"] = rc == RT_CANCELLED
     return rgb, sub, out

@@ -19,7 +19,8 @@ Run:  PORT=8080 python -m rt_amd.server <scenes dir>
       §13): RT_PROGRESSIVE gives the first frame's spp, the request's spp is the per-pixel budget.
       RT_TARGET_BATCH=<C>[,<gain>] together with RT_TARGET_ERROR: up to <C> (1..16) sparse passes per pixel run in one
       launch, each batch handing out <gain> (in (0, 1]; default: rt_amd.ERROR_TARGET_BATCH_DEFAULTS) of a pixel's
-      predicted need (rt_amd.render_to_error's batch and gain). Unset: the sequential loop.
+      predicted need (rt_amd.render_to_error's batch and gain; a mesh scene's batches run its own pool
+      kernel, §18). Unset: the sequential loop.
       RT_REPROJECT=<max_n> together with RT_PROGRESSIVE or RT_TARGET_ERROR: a connection keeps its last accumulator
       and view, and a request for the same scene starts from the reprojected history (rt_amd.render_interactive,
       DESIGN.md §14; at most max_n samples per subpixel are inherited).

@@ -19,13 +19,18 @@
       with the same pass sizes taken to the first total at or above the mean spp. These figures choose
       rt_amd.ERROR_TARGET_DEFAULTS.
   python tools/adapt_probe.py batch [--size 1920x1080] [--scenes cornell_box,cubes,flying_unicorn] [--batch C --gain g]
-                                    [--log profiles/batch_time.log]
-      DESIGN.md §17: the sequential error-target loop (rt_accum_select_device, rt_render_pixels_device with the scene's
-      own list family, rt_accum_add_sub_pixels_device) and the batched one (rt_accum_refine: the fused body's
-      k_render_passes_f64) side by side in one process, a step of each in turn, on two accumulators that start from the
+                                    [--family auto|fused] [--log profiles/batch_time.log]
+      DESIGN.md §17, §18: the sequential error-target loop (rt_accum_select_device, rt_render_pixels_device with the
+      scene's own list family, rt_accum_add_sub_pixels_device) and the batched one (rt_accum_refine: the passes instance
+      of the scene's own family) side by side in one process, a step of each in turn, on two accumulators that start from the
       same two 8-spp passes; abs_tol 0.04, pass_spp 16, max_spp 496. Per loop: render launches, the wall time from the
       first selection to the last merge (every call waits for its work), the renders' device time (HIP events around
       the render kernels, rt_render_stats.device_ms), Msamples/s per launch (median, first, last), mean spp.
+      --family fused: the batched loop's renders on the fused body's k_render_passes_f64 for every scene, as before the
+      pools had passes instances. rt_accum_refine has no family argument, so this loop is its restatement in public
+      calls: rt_accum_plan_device, rt_render_pixel_passes_with_device(RT_LIST_FUSED), then per pass i one
+      rt_accum_add_sub_pixels_device of the entries with counts[e] > i (the bits of the run merge, in more launches:
+      compare the render time; the wall time carries those merges and the gathers between them).
 """
 import argparse
 import ctypes
@@ -298,7 +303,7 @@ def cmd_batch(args):
     ids_d = torch.zeros(npix, dtype=torch.int32, device=dev)
     lsub = torch.zeros(npix * 12, dtype=torch.float64, device=dev)
     log(f"# adapt_probe batch: {w}x{h}, abs_tol {abs_tol}, two 8-spp passes, then passes of {spp} spp to max_spp 496; "
-        f"batched: C = {C}, gain = {gain}; seeds pass_seed({seed}, k); one process, a step of each loop in turn")
+        f"batched: C = {C}, gain = {gain}, family {args.family}; seeds pass_seed({seed}, k); one process, a step of each loop in turn")
     log("scene            loop        list family  launches  wall ms  render ms  Ms/s per launch median (first, last)  "
         "mean spp")
     for name in args.scenes.split(","):
@@ -337,7 +342,39 @@ def cmd_batch(args):
             r["wall"] += time.perf_counter() - t0
             return n, stats.device_ms, stats.samples
 
+        cnt_d = torch.zeros(npix, dtype=torch.uint8, device=dev)
+        units_out, used_out = ctypes.c_int64(), ctypes.c_int64()
+
+        def step_bat_fused(r):
+            t0 = time.perf_counter()
+            rt_amd._check(rt_amd.lib.rt_accum_plan_device(bat.handle, abs_tol, 0.0, max_n, spp // 4, gain, C,
+                                                          V(ids_d.data_ptr()), V(cnt_d.data_ptr()), npix,
+                                                          ctypes.byref(n_out), ctypes.byref(units_out),
+                                                          ctypes.byref(used_out), st))
+            n, units, used = n_out.value, units_out.value, used_out.value
+            if n:
+                sd = np.array([rt_amd.pass_seed(seed, r["k"] + i) % (1 << 64) for i in range(C)], dtype=np.uint64)
+                rt_amd._check(rt_amd.lib.rt_render_pixel_passes_with_device(
+                    sc.handle, ctypes.byref(p), V(ids_d.data_ptr()), V(cnt_d.data_ptr()), n, units,
+                    sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), C, rt_amd.LIST_FUSED, None, V(lsub.data_ptr()), st,
+                    ctypes.byref(stats)))
+                cnt = cnt_d[:n].to(torch.int64)
+                off = torch.cumsum(cnt, 0) - cnt
+                sub = lsub.view(-1, 12)
+                for i in range(used):
+                    m = cnt > i
+                    ids_i = ids_d[:n][m].contiguous()
+                    sub_i = sub[off[m] + i].contiguous()
+                    rt_amd._check(rt_amd.lib.rt_accum_add_sub_pixels_device(bat.handle, V(ids_i.data_ptr()), ids_i.numel(),
+                                                                            V(sub_i.data_ptr()), spp // 4, st))
+                    torch.cuda.synchronize()
+                r["k"] += used
+            r["wall"] += time.perf_counter() - t0
+            return n, stats.device_ms, stats.samples
+
         def step_bat(r):
+            if args.family == "fused":
+                return step_bat_fused(r)
             t0 = time.perf_counter()
             out = bat.refine(sc, spp, [rt_amd.pass_seed(seed, r["k"] + i) for i in range(C)], abs_tol, 0.0, max_n, gain)
             r["wall"] += time.perf_counter() - t0
@@ -359,7 +396,7 @@ def cmd_batch(args):
             r = run[key]
             rates = [s_ / m / 1e3 for s_, m in zip(r["samples"], r["ms"]) if m > 0]
             mean_spp = 4.0 * float(acc.counts()[1].mean())
-            log(f"{name:16s} {key:11s} {fam if key == 'sequential' else 'fused':11s} {len(r['ms']):9d} "
+            log(f"{name:16s} {key:11s} {fam if key == 'sequential' or args.family == 'auto' else 'fused':11s} {len(r['ms']):9d} "
                 f"{r['wall'] * 1e3:8.1f} {sum(r['ms']):10.1f}  {statistics.median(rates):10.1f} ({rates[0]:.1f}, "
                 f"{rates[-1]:.1f})" + " " * 12 + f"{mean_spp:8.2f}")
         s_, b_ = run["sequential"], run["batched"]
@@ -389,6 +426,8 @@ def main():
     b.add_argument("--scenes", default="cornell_box,cubes,flying_unicorn")
     b.add_argument("--batch", type=int, default=0, help="C (default: rt_amd.ERROR_TARGET_BATCH_DEFAULTS)")
     b.add_argument("--gain", type=float, default=0.0)
+    b.add_argument("--family", default="auto", choices=("auto", "fused"),
+                   help="the batched loop's kernel family: the scene's own (auto) or k_render_passes_f64 for every scene")
     b.add_argument("--log", default=os.path.join(REPO, "profiles", "batch_time.log"))
     b.set_defaults(fn=cmd_batch)
     args = ap.parse_args()
