@@ -85,10 +85,8 @@ RT_DEV SubPixel subpixel_of_pixel(const RenderArgs& a, uint32_t p, int u) {
     s.sy = s.sub >> 1;
     return s;
 }
-// What a unit list holds, for the fused body and the two pool bodies alike: nothing (kFrame: units are the tile's
-// subpixels), a frame pixel per unit-group (kList), or a (pixel, pass) word per unit-group
-// (kPasses): pixel | pass << kPassShift, the pass indexing a table of 16 seeds on the device.
-constexpr int kFrame = 0, kList = 1, kPasses = 2;
+// A passes unit word (kernels.h kPasses): pixel | pass << kPassShift, the pass indexing a table of
+// 16 seeds on the device.
 constexpr int kPassShift = 28;
 constexpr uint32_t kPassPixMask = (1u << kPassShift) - 1u;
 // The one place a pool kernel's unit id becomes a pixel: the frame instances (L = kFrame) map the tile-local id,

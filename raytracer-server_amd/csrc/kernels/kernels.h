@@ -77,13 +77,17 @@ int diag_read_flat(unsigned long long* cnt16, unsigned long long* reg32, unsigne
 hipError_t launch_megakernel_f32(const DevScene& sc, const RenderArgs& a, double* sub_buf, uint32_t* next_sub,
                                  hipStream_t st);
 hipError_t launch_finalize_f64(const RenderArgs& a, const double* sub_buf, hipStream_t st);
-// Pixel-list render (render_f64.hip): the subpixel means of the n_pixels frame pixels
-// pixels[e] = row * width + col (device, unique ids < width * height) into sub_buf[e][4][3]; a.tw / th / x0 / y0 /
-// row_step play no part. n_pixels * 4 <= INT32_MAX. next_unit: the ticket counter (reset here).
-// family (include/rt_ffi.h RT_LIST_*): kListFused runs k_render_list_f64, the list instance of the fused megakernel's
-// body with its Cfg choice (a.features & 15); kListFpool / kListRoles run the list instances of the frame's pool kernels
-// (launch_render_list_flat_f64 / launch_render_list_roles_f64), which must be list_pool_family's answer for the
-// scene (hipErrorInvalidValue otherwise); tail_buf / tail_cap: their split-tail scratch, as launch_megakernel_f64's.
+// What a launch's units are, for the fused body and the two pool bodies alike: nothing (kFrame: units are the tile's
+// subpixels), a frame pixel per unit-group (kList), or a (pixel, pass) word per unit-group
+// (kPasses): pixel | pass << kPassShift (integrator_f64.h), the pass indexing a table of 16 seeds.
+constexpr int kFrame = 0, kList = 1, kPasses = 2;
+struct UnitList {           // device pointers
+    const uint32_t* words;  // n entries: unique pixel ids (list) or pixel | pass << 28 (passes); null: a frame
+    long n;
+    const uint64_t* seeds;  // 16 seeds: non-null makes it a passes list
+    int kind() const { return seeds ? kPasses : words ? kList : kFrame; }
+};
+// The kernel families with list and passes instances (include/rt_ffi.h RT_LIST_*).
 enum : int { kListFused = 1, kListFpool = 2, kListRoles = 3 };
 // The pool kernel family launch_megakernel_f64 takes for these args that also has list instances, by its own
 // predicates; kListFused: none (analytic scenes, Phong mesh scenes, octrees without slot tables, BVH walks).
@@ -93,29 +97,22 @@ inline int list_pool_family(const RenderArgs& a, bool slot_tables) {
     if ((a.features & 9) == 9 && a.mesh_nodes >= 64 && slot_tables) return kListRoles;
     return kListFused;
 }
-hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
-                                  double* sub_buf, uint32_t* next_unit, int family, double* tail_buf, size_t tail_cap,
-                                  hipStream_t st);
-// Batched passes (render_f64.hip): unit-group u renders frame pixel units[u] & (2^28 - 1) with the
-// seed seeds[units[u] >> 28] (device: n_units words, 16 seeds) into sub_buf[u][4][3]; width * height < 2^28 and
-// n_units * 4 <= INT32_MAX (hipErrorInvalidValue otherwise). family, tail_buf, tail_cap: as launch_render_list_f64's
-// (kListFused: k_render_passes_f64; kListFpool / kListRoles: the passes instances of the scene's pool kernel,
-// launch_render_passes_flat_f64 / launch_render_passes_roles_f64, which must be list_pool_family's answer).
-hipError_t launch_render_passes_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* units, long n_units,
-                                    const uint64_t* seeds, double* sub_buf, uint32_t* next_unit, int family,
-                                    double* tail_buf, size_t tail_cap, hipStream_t st);
-hipError_t launch_render_passes_flat_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* units, long n_units,
-                                         const uint64_t* seeds, double* sub_buf, uint32_t* next_sub, double* tail_buf,
-                                         size_t tail_cap, hipStream_t st);
-hipError_t launch_render_passes_roles_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* units, long n_units,
-                                          const uint64_t* seeds, double* sub_buf, uint32_t* next_sub, double* tail_buf,
-                                          size_t tail_cap, hipStream_t st);
-hipError_t launch_render_list_flat_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
-                                       double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
-                                       hipStream_t st);
-hipError_t launch_render_list_roles_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
-                                        double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
-                                        hipStream_t st);
+// Pixel-list render and batched passes (render_f64.hip): the subpixel means of unit-group u
+// into sub_buf[u][4][3]: of the frame pixel units.words[u] with a.seed (kList), or of the frame pixel
+// units.words[u] & (2^28 - 1) with the seed units.seeds[units.words[u] >> 28] (kPasses: width * height < 2^28,
+// hipErrorInvalidValue otherwise); a.tw / th / x0 / y0 / row_step play no part. units.n * 4 <= INT32_MAX and
+// non-null words (hipErrorInvalidValue otherwise). next_unit: the ticket counter (reset here).
+// family kListFused runs k_render_list_f64 / k_render_passes_f64, the list and passes instances of the fused
+// megakernel's body with its Cfg choice (a.features & 15); kListFpool / kListRoles run the list or passes instances of
+// the frame's pool kernels (launch_render_units_flat_f64 / launch_render_units_roles_f64, called after the ticket
+// counter is reset), which must be list_pool_family's answer for the scene (hipErrorInvalidValue otherwise);
+// tail_buf / tail_cap: their split-tail scratch, as launch_megakernel_f64's.
+hipError_t launch_render_units_f64(const DevScene& sc, const RenderArgs& a, const UnitList& units, double* sub_buf,
+                                   uint32_t* next_unit, int family, double* tail_buf, size_t tail_cap, hipStream_t st);
+hipError_t launch_render_units_flat_f64(const DevScene& sc, const RenderArgs& a, const UnitList& units, double* sub_buf,
+                                        uint32_t* next_sub, double* tail_buf, size_t tail_cap, hipStream_t st);
+hipError_t launch_render_units_roles_f64(const DevScene& sc, const RenderArgs& a, const UnitList& units, double* sub_buf,
+                                         uint32_t* next_sub, double* tail_buf, size_t tail_cap, hipStream_t st);
 hipError_t launch_trace_f64(const DevScene& sc, long n, const double* o, const double* d, double* t, int32_t* obj,
                             double* pos, double* nrm, bool mesh_nearest, hipStream_t st);
 

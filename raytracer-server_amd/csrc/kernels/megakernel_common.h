@@ -234,6 +234,16 @@ static inline long resident_blocks(K kernel, long want, int threads = 256) {
     return std::max(1L, std::min((long)ncu * per_cu, want));
 }
 
+// Launches the instance `kernel` of a megakernel for unit kind L (kernels.h UnitList): `args` are the frame
+// instance's; a list instance takes the unit words after them, a passes instance the words and the seeds.
+template <int L, class K, class... A>
+static inline void launch_units(K kernel, long blocks, int threads, hipStream_t st, const UnitList& u, const A&... args) {
+    const dim3 grid((unsigned)blocks), block((unsigned)threads);
+    if constexpr (L == kPasses) hipLaunchKernelGGL(kernel, grid, block, 0, st, args..., u.words, u.seeds);
+    else if constexpr (L == kList) hipLaunchKernelGGL(kernel, grid, block, 0, st, args..., u.words);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
+}
+
 // A/B overrides (ab_knobs.h): RT_* environment variables in -DRT_AB_KNOBS=1 builds only
 static inline int env_int(const char* name, int dflt) { return (int)ab_knob(name, dflt); }
 

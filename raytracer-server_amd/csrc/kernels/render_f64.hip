@@ -3,10 +3,10 @@
 //   k_megakernel_f64  — fused, persistent path loop (below); k_finalize_f64 — subpixel means -> RGB8.
 //   k_render_list_f64 — the same loop over a list of frame pixels: analytic scenes, and mesh scenes
 //                       whose frame kernel has no list instance (Phong mesh scenes, octrees without slot tables) or
-//                       whose list is short; launch_render_list_f64 hands the other mesh scenes' lists to the list
+//                       whose list is short; launch_render_units_f64 hands the other mesh scenes' lists to the list
 //                       instances of the frame's own pool kernels, which give the same bits.
 //   k_render_passes_f64 — the same loop over a list of (pixel, pass) units with a seed per pass;
-//                       launch_render_passes_f64 hands the scenes with pool list instances to the pools' passes
+//                       launch_render_units_f64 hands the scenes with pool list instances to the pools' passes
 //                       instances.
 //   k_trace_f64       — Scene::trace_ray for a batch of rays (parity tests of the intersectors).
 //   wavefront kernels — see wavefront_f64.hip.
@@ -556,40 +556,44 @@ hipError_t launch_diag_sincos(long n, const double* x, double* s, double* c, hip
 
 thread_local TailPlan t_tail_plan;
 
-// One launch of the fused body. A frame (L = false) plans its split tail and sums it afterwards; a pixel list
-// (L = true: nsub = a.n_whole = 4 n_pixels) is handed out in runs of whole units only, with no split tail.
-template <int F, int W, bool L>
+// The instance of the fused body for (F, W) and unit kind L.
+template <int F, int W, int L>
+constexpr auto mk_kernel() {
+    if constexpr (L == kPasses) return &k_render_passes_f64<F, W>;
+    else if constexpr (L == kList) return &k_render_list_f64<F, W>;
+    else return &k_megakernel_f64<F, W>;
+}
+
+// One launch of the fused body. A frame (L = kFrame) plans its split tail and sums it afterwards; a pixel list or a
+// list of passes (nsub = a.n_whole = 4 units.n) is handed out in runs of whole units only, with no split tail.
+template <int F, int W, int L>
 static void launch_mk(const DevScene& sc, const RenderArgs& a_in, double* sub_buf, uint32_t* next_sub, long nsub,
-                      int refill, double* tail_buf, size_t tail_cap, const uint32_t* pixels, hipStream_t st) {
+                      int refill, double* tail_buf, size_t tail_cap, const UnitList& units, hipStream_t st) {
     RenderArgs a = a_in;
-    if constexpr (L) {
-        const long blocks = resident_blocks(k_render_list_f64<F, W>, (nsub + 255) / 256);
-        plan_units(a, blocks * 256, 256, RT_MK_MIN_RUN);
-        hipLaunchKernelGGL((k_render_list_f64<F, W>), dim3((unsigned)blocks), dim3(256), 0, st, sc, a, sub_buf, next_sub,
-                           nsub, refill, pixels);
-    } else {
-        const long blocks = resident_blocks(k_megakernel_f64<F, W>, (nsub + 255) / 256);
+    constexpr auto kernel = mk_kernel<F, W, L>();
+    const long blocks = resident_blocks(kernel, (nsub + 255) / 256);
+    if constexpr (L == kFrame)
         plan_tail(a, nsub, blocks * 256, tail_buf, tail_cap, tail_split_x2(nsub, blocks * 256), 2, 256, RT_MK_MIN_RUN);
-        hipLaunchKernelGGL((k_megakernel_f64<F, W>), dim3((unsigned)blocks), dim3(256), 0, st, sc, a, sub_buf, next_sub,
-                           nsub, refill);
-        launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
-    }
+    else
+        plan_units(a, blocks * 256, 256, RT_MK_MIN_RUN);
+    launch_units<L>(kernel, blocks, 256, st, units, sc, a, sub_buf, next_sub, nsub, refill);
+    launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);  // (nothing for a list: nsub == a.n_whole)
 }
 
 // The analytic / fused-mesh megakernel at its waves/SIMD: 4 for analytic scenes, 3 with meshes (the defaults);
 // A/B builds (ab_knobs.h) compile both shapes of every frame instance for RT_MK_WAVES.
-template <int F, bool L>
+template <int F, int L>
 static void launch_mk_shape(int waves, const DevScene& sc, const RenderArgs& a, double* sub_buf, uint32_t* next_sub,
-                            long nsub, int refill, double* tail_buf, size_t tail_cap, const uint32_t* pixels,
+                            long nsub, int refill, double* tail_buf, size_t tail_cap, const UnitList& units,
                             hipStream_t st) {
     (void)waves;
-    if constexpr (RT_AB_KNOBS != 0 && !L) {
-        if (waves == 3) launch_mk<F, 3, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);
-        else launch_mk<F, RT_MK_W4, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);
+    if constexpr (RT_AB_KNOBS != 0 && L == kFrame) {
+        if (waves == 3) launch_mk<F, 3, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, units, st);
+        else launch_mk<F, RT_MK_W4, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, units, st);
     } else if constexpr ((F & 1) != 0) {
-        launch_mk<F, 3, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);
+        launch_mk<F, 3, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, units, st);
     } else {
-        launch_mk<F, RT_MK_W4, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);
+        launch_mk<F, RT_MK_W4, L>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, units, st);
     }
 }
 
@@ -600,14 +604,14 @@ static int cam_refill() {
     return refill;
 }
 
-// The fused instance of a.features & 15, for a frame or a pixel list.
-template <bool L>
+// The fused instance of a.features & 15, for a frame, a pixel list or a list of passes.
+template <int L>
 static void launch_mk_features(int waves, const DevScene& sc, const RenderArgs& a, double* sub_buf, uint32_t* next_sub,
-                               long nsub, double* tail_buf, size_t tail_cap, const uint32_t* pixels, hipStream_t st) {
+                               long nsub, double* tail_buf, size_t tail_cap, const UnitList& units, hipStream_t st) {
     const int refill = cam_refill();
 #define RT_MK_CASE(F)                                                                                              \
     case F:                                                                                                        \
-        launch_mk_shape<F, L>(waves, sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, pixels, st);      \
+        launch_mk_shape<F, L>(waves, sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, units, st);       \
         break;
     switch (a.features & 15) {
         RT_MK_CASE(0) RT_MK_CASE(1) RT_MK_CASE(2) RT_MK_CASE(3) RT_MK_CASE(4) RT_MK_CASE(5) RT_MK_CASE(6)
@@ -653,7 +657,7 @@ hipError_t launch_megakernel_f64(const DevScene& sc, const RenderArgs& a_in, dou
         // traversal inline, 3 waves/SIMD
 #define RT_MB_CASE(F)                                                                             \
     case F:                                                                                       \
-        launch_mk<F, 3, false>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, nullptr, st); \
+        launch_mk<F, 3, kFrame>(sc, a, sub_buf, next_sub, nsub, refill, tail_buf, tail_cap, UnitList{}, st); \
         break;
         switch (a.features & 31) {
             RT_MB_CASE(17) RT_MB_CASE(19) RT_MB_CASE(21) RT_MB_CASE(23) RT_MB_CASE(25) RT_MB_CASE(27) RT_MB_CASE(29)
@@ -662,20 +666,22 @@ hipError_t launch_megakernel_f64(const DevScene& sc, const RenderArgs& a_in, dou
 #undef RT_MB_CASE
         return hipGetLastError();
     }
-    launch_mk_features<false>(waves, sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, st);
+    launch_mk_features<kFrame>(waves, sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, UnitList{}, st);
     return hipGetLastError();
 }
 
-// Pixel-list render. family kListFused: the fused body's list instance, with the frame's Cfg
-// choice, mesh instances at 3 waves/SIMD and analytic ones at RT_MK_W4; kListFpool / kListRoles: the list instances
-// of the scene's pool kernel. RT_FLAG_FP32 and RT_FLAG_MESH_NEAREST are out of scope (rt_api.cpp returns RT_E_INVAL).
-hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* pixels, long n_pixels,
-                                  double* sub_buf, uint32_t* next_unit, int family, double* tail_buf, size_t tail_cap,
-                                  hipStream_t st) {
-    if (n_pixels <= 0 || a_in.n_samples <= 0) return hipSuccess;
-    if (n_pixels > 0x7fffffffL / 4) return hipErrorInvalidValue;
+// Pixel-list render and batched passes. family kListFused: the fused body's kList or kPasses
+// instance of a.features & 15, with the frame's Cfg choice, mesh instances at 3 waves/SIMD and analytic ones at
+// RT_MK_W4, handed out in runs of whole units (plan_units, no split tail); kListFpool / kListRoles: the list or passes
+// instances of the scene's pool kernel, planned as its frame is (split tail included). RT_FLAG_FP32 and
+// RT_FLAG_MESH_NEAREST are out of scope (rt_api.cpp returns RT_E_INVAL).
+hipError_t launch_render_units_f64(const DevScene& sc, const RenderArgs& a_in, const UnitList& units, double* sub_buf,
+                                   uint32_t* next_unit, int family, double* tail_buf, size_t tail_cap, hipStream_t st) {
+    if (units.n <= 0 || a_in.n_samples <= 0) return hipSuccess;
+    if (units.n > 0x7fffffffL / 4 || !units.words) return hipErrorInvalidValue;
+    if (units.seeds && (long)a_in.width * a_in.height > (long)kPassPixMask) return hipErrorInvalidValue;
     RenderArgs a = a_in;
-    a.n_whole = (int32_t)(n_pixels * 4);  // every unit is a whole subpixel unless a pool launcher plans a split tail
+    a.n_whole = (int32_t)(units.n * 4);  // every unit is a whole subpixel unless a pool launcher plans a split tail
     a.chunk_lg = 0;
     a.tail_cps = 1;
     a.tail_buf = nullptr;
@@ -686,57 +692,11 @@ hipError_t launch_render_list_f64(const DevScene& sc, const RenderArgs& a_in, co
     // instance of is an error, never a quiet change of kernel
     if (family != kListFused) {
         if (family != list_pool_family(a, sc.node_slot != nullptr)) return hipErrorInvalidValue;
-        if (family == kListFpool)
-            return launch_render_list_flat_f64(sc, a, pixels, n_pixels, sub_buf, next_unit, tail_buf, tail_cap, st);
-        return launch_render_list_roles_f64(sc, a, pixels, n_pixels, sub_buf, next_unit, tail_buf, tail_cap, st);
+        if (family == kListFpool) return launch_render_units_flat_f64(sc, a, units, sub_buf, next_unit, tail_buf, tail_cap, st);
+        return launch_render_units_roles_f64(sc, a, units, sub_buf, next_unit, tail_buf, tail_cap, st);
     }
-    launch_mk_features<true>(0, sc, a, sub_buf, next_unit, a.n_whole, nullptr, 0, pixels, st);
-    return hipGetLastError();
-}
-
-// Batched passes. family kListFused: the fused body's kPasses instance of a.features & 15 over
-// n_units (pixel, pass) words; mesh instances at 3 waves/SIMD and analytic ones at RT_MK_W4, planned like a pixel list
-// (plan_units, no split tail). kListFpool / kListRoles: the passes instances of the scene's pool kernel, planned as
-// their list instances are (split tail included).
-template <int F>
-static void launch_mk_passes(const DevScene& sc, RenderArgs a, double* sub_buf, uint32_t* next_unit, int refill,
-                             const uint32_t* units, const uint64_t* seeds, hipStream_t st) {
-    constexpr int W = (F & 1) ? 3 : RT_MK_W4;
-    const long nsub = a.n_whole;
-    const long blocks = resident_blocks(k_render_passes_f64<F, W>, (nsub + 255) / 256);
-    plan_units(a, blocks * 256, 256, RT_MK_MIN_RUN);
-    hipLaunchKernelGGL((k_render_passes_f64<F, W>), dim3((unsigned)blocks), dim3(256), 0, st, sc, a, sub_buf, next_unit,
-                       nsub, refill, units, seeds);
-}
-hipError_t launch_render_passes_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* units, long n_units,
-                                    const uint64_t* seeds, double* sub_buf, uint32_t* next_unit, int family,
-                                    double* tail_buf, size_t tail_cap, hipStream_t st) {
-    if (n_units <= 0 || a_in.n_samples <= 0) return hipSuccess;
-    if (n_units > 0x7fffffffL / 4 || (long)a_in.width * a_in.height > (long)kPassPixMask || !units || !seeds)
-        return hipErrorInvalidValue;
-    RenderArgs a = a_in;
-    a.n_whole = (int32_t)(n_units * 4);
-    a.chunk_lg = 0;
-    a.tail_cps = 1;
-    a.tail_buf = nullptr;
-    t_tail_plan = TailPlan{};
-    hipError_t e = hipMemsetAsync(next_unit, 0, sizeof(uint32_t), st);
-    if (e != hipSuccess) return e;
-    // a family the scene has no instance of is an error, never a quiet change of kernel (launch_render_list_f64's rule)
-    if (family != kListFused) {
-        if (family != list_pool_family(a, sc.node_slot != nullptr)) return hipErrorInvalidValue;
-        if (family == kListFpool)
-            return launch_render_passes_flat_f64(sc, a, units, n_units, seeds, sub_buf, next_unit, tail_buf, tail_cap, st);
-        return launch_render_passes_roles_f64(sc, a, units, n_units, seeds, sub_buf, next_unit, tail_buf, tail_cap, st);
-    }
-    const int refill = cam_refill();
-#define RT_MP_CASE(F) case F: launch_mk_passes<F>(sc, a, sub_buf, next_unit, refill, units, seeds, st); break;
-    switch (a.features & 15) {
-        RT_MP_CASE(0) RT_MP_CASE(1) RT_MP_CASE(2) RT_MP_CASE(3) RT_MP_CASE(4) RT_MP_CASE(5) RT_MP_CASE(6)
-        RT_MP_CASE(7) RT_MP_CASE(8) RT_MP_CASE(9) RT_MP_CASE(10) RT_MP_CASE(11) RT_MP_CASE(12) RT_MP_CASE(13)
-        RT_MP_CASE(14) RT_MP_CASE(15)
-    }
-#undef RT_MP_CASE
+    if (units.kind() == kPasses) launch_mk_features<kPasses>(0, sc, a, sub_buf, next_unit, a.n_whole, nullptr, 0, units, st);
+    else launch_mk_features<kList>(0, sc, a, sub_buf, next_unit, a.n_whole, nullptr, 0, units, st);
     return hipGetLastError();
 }
 

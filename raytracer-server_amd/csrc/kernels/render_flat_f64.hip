@@ -890,23 +890,19 @@ __global__ __launch_bounds__(B, W) void k_megakernel_fpool_passes_f64(DevScene s
 // One launch of the query pool, with its split tail planned: a frame (L = kFrame), a pixel list (kList: nsub =
 // 4 n_pixels compact units) or a list of (pixel, pass) words with their seeds (kPasses: nsub = 4 n_units).
 template <int F, int W, int B, int L>
+constexpr auto fpool_kernel() {
+    if constexpr (L == kPasses) return &k_megakernel_fpool_passes_f64<F, W, B>;
+    else if constexpr (L == kList) return &k_megakernel_fpool_list_f64<F, W, B>;
+    else return &k_megakernel_fpool_f64<F, W, B>;
+}
+template <int F, int W, int B, int L>
 static void launch_fpool(const DevScene& sc, RenderArgs& a, double* sub_buf, uint32_t* next_sub, long nsub,
-                         double* tail_buf, size_t tail_cap, int pool_min, int refill, const uint32_t* pixels,
-                         const uint64_t* seeds, hipStream_t st) {
-    long blocks;
-    if constexpr (L == kPasses) blocks = resident_blocks(k_megakernel_fpool_passes_f64<F, W, B>, (nsub + B - 1) / B, B);
-    else if constexpr (L == kList) blocks = resident_blocks(k_megakernel_fpool_list_f64<F, W, B>, (nsub + B - 1) / B, B);
-    else blocks = resident_blocks(k_megakernel_fpool_f64<F, W, B>, (nsub + B - 1) / B, B);
+                         double* tail_buf, size_t tail_cap, int pool_min, int refill, const UnitList& units,
+                         hipStream_t st) {
+    constexpr auto kernel = fpool_kernel<F, W, B, L>();
+    const long blocks = resident_blocks(kernel, (nsub + B - 1) / B, B);
     plan_tail(a, nsub, blocks * B, tail_buf, tail_cap, tail_split_x2(nsub, blocks * B));
-    if constexpr (L == kPasses)
-        hipLaunchKernelGGL((k_megakernel_fpool_passes_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                           next_sub, nsub, pool_min, refill, pixels, seeds);
-    else if constexpr (L == kList)
-        hipLaunchKernelGGL((k_megakernel_fpool_list_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                           next_sub, nsub, pool_min, refill, pixels);
-    else
-        hipLaunchKernelGGL((k_megakernel_fpool_f64<F, W, B>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                           next_sub, nsub, pool_min, refill);
+    launch_units<L>(kernel, blocks, B, st, units, sc, a, sub_buf, next_sub, nsub, pool_min, refill);
 }
 
 template <int F, int W>
@@ -942,12 +938,11 @@ static bool fpool_nospec(const RenderArgs& a) {
 // have no Phong instances.
 template <int L>
 static hipError_t launch_fpool_product(const DevScene& sc, RenderArgs& a, double* sub_buf, uint32_t* next_sub, long nsub,
-                                       double* tail_buf, size_t tail_cap, const uint32_t* pixels, const uint64_t* seeds,
-                                       hipStream_t st) {
+                                       double* tail_buf, size_t tail_cap, const UnitList& units, hipStream_t st) {
     if (L != kFrame && (a.features & 2)) return hipErrorInvalidValue;  // Phong scenes stay on the fused body's instances
 #define RT_FPOOL_CASE(F, W, B, LL)                                                                                        \
     case (F) & 15:                                                                                                        \
-        launch_fpool<F, W, B, LL>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), pixels, seeds, st); \
+        launch_fpool<F, W, B, LL>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), units, st); \
         break;
     if (fpool_nospec(a)) {
         switch (a.features & 15) {
@@ -982,7 +977,7 @@ hipError_t launch_megakernel_flat_f64(const DevScene& sc, const RenderArgs& a_in
     if (!fpool || (waves == 2 && !fpool_nospec(a))) {
 #define RT_FLAT_CASE(F)                                                                                                   \
     case F:                                                                                                               \
-        if (fpool) launch_fpool<F, 2, kBlk, kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), nullptr, nullptr, st); \
+        if (fpool) launch_fpool<F, 2, kBlk, kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, fpool_min(), fpool_refill(), UnitList{}, st); \
         else if (waves == 2) launch_flat<F, 2>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st);                   \
         else launch_flat<F, 3>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, st);                                   \
         break;
@@ -995,26 +990,21 @@ hipError_t launch_megakernel_flat_f64(const DevScene& sc, const RenderArgs& a_in
         return hipGetLastError();
     }
 #endif
-    return launch_fpool_product<kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, nullptr, st);
+    return launch_fpool_product<kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, UnitList{}, st);
 }
 
-// The query pool over a pixel list (kernels.h list_pool_family == kListFpool: flat octrees, no Phong
-// object): the frame's product instances and planning with nsub = 4 n_pixels compact units, the split tail included.
-// Called by launch_render_list_f64 after the ticket counter is reset.
-hipError_t launch_render_list_flat_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* pixels, long n_pixels,
-                                       double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
-                                       hipStream_t st) {
+// The query pool over a pixel list or a list of (pixel, pass) words (kernels.h list_pool_family ==
+// kListFpool: flat octrees, no Phong object): the frame's product dispatch and planning with the list or passes
+// instances and nsub = 4 units.n compact units, the split tail included. Called by launch_render_units_f64 after the
+// ticket counter is reset.
+hipError_t launch_render_units_flat_f64(const DevScene& sc, const RenderArgs& a_in, const UnitList& units, double* sub_buf,
+                                        uint32_t* next_sub, double* tail_buf, size_t tail_cap, hipStream_t st) {
     RenderArgs a = a_in;
-    return launch_fpool_product<kList>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, nullptr, st);
-}
-
-// The query pool over a list of (pixel, pass) words: the list launcher with the passes instances,
-// nsub = 4 n_units compact units. Called by launch_render_passes_f64 after the ticket counter is reset.
-hipError_t launch_render_passes_flat_f64(const DevScene& sc, const RenderArgs& a_in, const uint32_t* units, long n_units,
-                                         const uint64_t* seeds, double* sub_buf, uint32_t* next_sub, double* tail_buf,
-                                         size_t tail_cap, hipStream_t st) {
-    RenderArgs a = a_in;
-    return launch_fpool_product<kPasses>(sc, a, sub_buf, next_sub, n_units * 4, tail_buf, tail_cap, units, seeds, st);
+    switch (units.kind()) {
+        case kList: return launch_fpool_product<kList>(sc, a, sub_buf, next_sub, units.n * 4, tail_buf, tail_cap, units, st);
+        case kPasses: return launch_fpool_product<kPasses>(sc, a, sub_buf, next_sub, units.n * 4, tail_buf, tail_cap, units, st);
+        default: return hipErrorInvalidValue;  // a frame: launch_megakernel_flat_f64
+    }
 }
 
 // rt_diag_trace / rt_diag_visible, the flat query pool's split of a query (RenderArgs::all_flat scenes): the

@@ -1264,27 +1264,23 @@ __global__ __launch_bounds__(B, W) void k_megakernel_roles_passes_f64(DevScene s
 
 // One launch of the role-split pool, its split tail planned and summed: a frame (L = kFrame), a pixel list (kList:
 // nsub = 4 n_pixels compact units) or a list of (pixel, pass) words with their seeds (kPasses: nsub = 4 n_units).
+template <int F, int W, bool S, int L>
+constexpr auto roles_kernel() {
+    if constexpr (L == kPasses) return &k_megakernel_roles_passes_f64<F, W, S>;
+    else if constexpr (L == kList) return &k_megakernel_roles_list_f64<F, W, S>;
+    else return &k_megakernel_roles_f64<F, W, S>;
+}
 template <int F, int L, bool S = (RT_WALK_TIGHT != 0)>
 static void launch_roles(const DevScene& sc, const RenderArgs& a_in, double* sub_buf, uint32_t* next_sub, long nsub,
-                         double* tail_buf, size_t tail_cap, const uint32_t* pixels, const uint64_t* seeds, hipStream_t st) {
+                         double* tail_buf, size_t tail_cap, const UnitList& units, hipStream_t st) {
     constexpr int B = RoleShape<Cfg<F>>::block, W = B / 256;  // one block per CU: B / 256 waves per SIMD
-    long blocks;
-    if constexpr (L == kPasses) blocks = resident_blocks(k_megakernel_roles_passes_f64<F, W, S>, (nsub + B - 1) / B, B);
-    else if constexpr (L == kList) blocks = resident_blocks(k_megakernel_roles_list_f64<F, W, S>, (nsub + B - 1) / B, B);
-    else blocks = resident_blocks(k_megakernel_roles_f64<F, W, S>, (nsub + B - 1) / B, B);
+    constexpr auto kernel = roles_kernel<F, W, S, L>();
+    const long blocks = resident_blocks(kernel, (nsub + B - 1) / B, B);
     RenderArgs a = a_in;
     // the split tail and ticket runs planned for the lanes that hold paths (one path slot per thread)
     // six subpixels per path slot; runs of whole subpixels of ~64 samples (plan_units)
     plan_tail(a, nsub, blocks * RoleLayout<Cfg<F>>::paths, tail_buf, tail_cap, 12, 1, 64);
-    if constexpr (L == kPasses)
-        hipLaunchKernelGGL((k_megakernel_roles_passes_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                           next_sub, nsub, pixels, seeds);
-    else if constexpr (L == kList)
-        hipLaunchKernelGGL((k_megakernel_roles_list_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                           next_sub, nsub, pixels);
-    else
-        hipLaunchKernelGGL((k_megakernel_roles_f64<F, W, S>), dim3((unsigned)blocks), dim3(B), 0, st, sc, a, sub_buf,
-                           next_sub, nsub);
+    launch_units<L>(kernel, blocks, B, st, units, sc, a, sub_buf, next_sub, nsub);
     launch_tail_sum_f64(a, sub_buf, nsub - a.n_whole, st);
 }
 
@@ -1329,7 +1325,7 @@ hipError_t launch_megakernel_mesh_f64(const DevScene& sc, const RenderArgs& a, d
     case F:                                                                                    \
         if (!sc.node_slot) launch_mm<F, 2, 1, false>(sc, a, sub_buf, next_sub, nsub, pool_ksteps, wmin, pool_refill, pool_min, pool_vmin, tail_buf, tail_cap, st); \
         RT_MM_AB(F)                                                                            \
-        else launch_roles<F, kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, nullptr, nullptr, st); \
+        else launch_roles<F, kFrame>(sc, a, sub_buf, next_sub, nsub, tail_buf, tail_cap, UnitList{}, st); \
         break;
 #define RT_MMB_CASE(F)                                                                         \
     case F:                                                                                    \
@@ -1347,32 +1343,27 @@ hipError_t launch_megakernel_mesh_f64(const DevScene& sc, const RenderArgs& a, d
 }
 
 // The role-split pool over a pixel list (kernels.h list_pool_family == kListRoles: compact scenes
-// with slot tables and an octree of >= 64 nodes, no Phong object): launch_roles with nsub = 4 n_pixels
-// compact units, the split tail included. Called by launch_render_list_f64 after the ticket counter is reset.
-hipError_t launch_render_list_roles_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* pixels, long n_pixels,
-                                        double* sub_buf, uint32_t* next_sub, double* tail_buf, size_t tail_cap,
-                                        hipStream_t st) {
-    if (!sc.node_slot) return hipErrorInvalidValue;  // octrees without slot tables stay on k_render_list_f64
+// with slot tables and an octree of >= 64 nodes, no Phong object), or over a list of (pixel, pass) words (DESIGN.md
+// §18): launch_roles with the list or passes instances and nsub = 4 units.n compact units, the split tail included.
+// Called by launch_render_units_f64 after the ticket counter is reset.
+template <int L>
+static hipError_t launch_roles_units(const DevScene& sc, const RenderArgs& a, const UnitList& units, double* sub_buf,
+                                     uint32_t* next_sub, double* tail_buf, size_t tail_cap, hipStream_t st) {
     switch (a.features & 31) {
-        case 9: launch_roles<9, kList>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, nullptr, st); break;
-        case 13: launch_roles<13, kList>(sc, a, sub_buf, next_sub, n_pixels * 4, tail_buf, tail_cap, pixels, nullptr, st); break;
+        case 9: launch_roles<9, L>(sc, a, sub_buf, next_sub, units.n * 4, tail_buf, tail_cap, units, st); break;
+        case 13: launch_roles<13, L>(sc, a, sub_buf, next_sub, units.n * 4, tail_buf, tail_cap, units, st); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
-
-// The role-split pool over a list of (pixel, pass) words: the list launcher with the passes
-// instances, nsub = 4 n_units compact units. Called by launch_render_passes_f64 after the ticket counter is reset.
-hipError_t launch_render_passes_roles_f64(const DevScene& sc, const RenderArgs& a, const uint32_t* units, long n_units,
-                                          const uint64_t* seeds, double* sub_buf, uint32_t* next_sub, double* tail_buf,
-                                          size_t tail_cap, hipStream_t st) {
-    if (!sc.node_slot) return hipErrorInvalidValue;  // octrees without slot tables stay on k_render_passes_f64
-    switch (a.features & 31) {
-        case 9: launch_roles<9, kPasses>(sc, a, sub_buf, next_sub, n_units * 4, tail_buf, tail_cap, units, seeds, st); break;
-        case 13: launch_roles<13, kPasses>(sc, a, sub_buf, next_sub, n_units * 4, tail_buf, tail_cap, units, seeds, st); break;
-        default: return hipErrorInvalidValue;
+hipError_t launch_render_units_roles_f64(const DevScene& sc, const RenderArgs& a, const UnitList& units, double* sub_buf,
+                                         uint32_t* next_sub, double* tail_buf, size_t tail_cap, hipStream_t st) {
+    if (!sc.node_slot) return hipErrorInvalidValue;  // octrees without slot tables stay on the fused body's instances
+    switch (units.kind()) {
+        case kList: return launch_roles_units<kList>(sc, a, units, sub_buf, next_sub, tail_buf, tail_cap, st);
+        case kPasses: return launch_roles_units<kPasses>(sc, a, units, sub_buf, next_sub, tail_buf, tail_cap, st);
+        default: return hipErrorInvalidValue;  // a frame: launch_megakernel_mesh_f64
     }
-    return hipGetLastError();
 }
 
 // The meshes' part of a split query, shared by the diagnostic kernels below: the slot walk of each mesh of `near` in

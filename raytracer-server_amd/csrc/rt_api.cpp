@@ -1100,7 +1100,7 @@ struct RenderCall {
         return e == hipSuccess ? RT_OK : oom_or_hip(e, who);
     }
 
-    // After render_enqueue / render_pixels_enqueue on cs.st returned rc: waits for the render while relaying the
+    // After render_enqueue / render_units_enqueue on cs.st returned rc: waits for the render while relaying the
     // cancel flag, copies back, completes the stats; RT_CANCELLED when the flag is up by then (the caller merges
     // nothing). An enqueue that failed left its message in g_err, and the stream is drained of whatever it did
     // enqueue before anything it used is released.
@@ -2156,14 +2156,23 @@ int list_family_of(const char* who, const rt_scene* s, const rt_render_params* p
     return RT_OK;
 }
 
-// render_enqueue for a pixel list (the list kernel of `path`'s family + k_finalize_f64 on the compact buffer);
-// arguments checked by check_render_pixels (and list_family_of for a path other than RT_LIST_AUTO), n_pixels > 0.
-// d_rgb and d_sub may be null.
-int render_pixels_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t* d_pixels, int64_t n_pixels,
-                          uint8_t* d_rgb, double* d_sub, hipStream_t st, const int32_t* dcancel, PendingStats* ps,
-                          int32_t path = RT_LIST_AUTO) {
+// An empty list launches nothing: no stats to speak of.
+int empty_list(rt_render_stats* stats) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    return RT_OK;
+}
+
+// render_enqueue for a device unit list (kernels.h UnitList, n > 0): a pixel list (what = "pixel-list render") or unit
+// words with their 16 device seeds (what = "batched render"; the family rule is the pixel list's). The
+// list or passes kernel of `path`'s family + k_finalize_f64 on the compact buffer; arguments checked by
+// check_render_pixels or check_passes (and list_family_of for a path other than RT_LIST_AUTO). d_rgb and d_sub may be null.
+constexpr const char* kListRender = "pixel-list render";
+constexpr const char* kBatchRender = "batched render";
+int render_units_enqueue(rt_scene* s, const rt_render_params* p, const rt::UnitList& units, uint8_t* d_rgb, double* d_sub,
+                         hipStream_t st, const int32_t* dcancel, PendingStats* ps, int32_t path, const char* what) {
+    const int64_t n = units.n;  // unit-groups: entries of the compact buffer
     int family = RT_LIST_FUSED;
-    int rc = list_family_of("pixel-list render", s, p, n_pixels, path, &family);
+    int rc = list_family_of(what, s, p, n, path, &family);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
     rt::DevScene ds;
@@ -2173,14 +2182,15 @@ int render_pixels_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t
     a.x0 = 0;
     a.y0 = 0;
     a.row_step = 1;
-    a.tw = (int32_t)n_pixels;  // k_finalize_f64's view of the compact buffer
+    a.tw = (int32_t)n;  // k_finalize_f64's view of the compact buffer
     a.th = 1;
+    if (units.seeds) a.seed = 0;  // unused: every unit draws from its pass's seed
     a.rgb_out = d_rgb;
     a.cancel = dcancel;
     if (ps) {
         const hipError_t e = ps->init(ps->out);
         if (e != hipSuccess) return fail(RT_E_HIP, std::string("stats: ") + hipGetErrorString(e));
-        ps->samples = n_pixels * 4 * (int64_t)a.n_samples;
+        ps->samples = n * 4 * (int64_t)a.n_samples;
         HIP_TRY(hipEventRecord(ps->e0, st));
     }
     hipError_t te;
@@ -2189,24 +2199,24 @@ int render_pixels_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t
     hipError_t e = ws->ensure_counters();
     double* sub = d_sub;
     if (e == hipSuccess && !sub) {
-        e = ws->ensure_sub((size_t)n_pixels);
+        e = ws->ensure_sub((size_t)n);
         sub = ws->sub_buf;
     }
     a.sub_out = sub;
     if (e == hipSuccess && ps) e = hipMemsetAsync(ws->counters, 0, 8 * sizeof(unsigned long long), st);
-    if (e == hipSuccess && a.n_samples <= 0) e = hipMemsetAsync(sub, 0, (size_t)n_pixels * 12 * sizeof(double), st);
+    if (e == hipSuccess && a.n_samples <= 0) e = hipMemsetAsync(sub, 0, (size_t)n * 12 * sizeof(double), st);
     if (e == hipSuccess) {
         a.counters = ps ? ws->counters : nullptr;
-        // the pool kernels split their last units into chunks of samples: the frame's scratch rule, for this many pixels
-        if (family != RT_LIST_FUSED) ensure_tail_scratch(ws.get(), a, (size_t)n_pixels);
-        e = rt::launch_render_list_f64(ds, a, d_pixels, (long)n_pixels, sub, (uint32_t*)(ws->counters + 4), family,
-                                       ws->tail_buf, ws->tail_cap, st);
+        // the pool kernels split their last units into chunks of samples: the frame's scratch rule, for this many unit-groups
+        if (family != RT_LIST_FUSED) ensure_tail_scratch(ws.get(), a, (size_t)n);
+        e = rt::launch_render_units_f64(ds, a, units, sub, (uint32_t*)(ws->counters + 4), family, ws->tail_buf,
+                                        ws->tail_cap, st);
     }
     if (e == hipSuccess && d_rgb) e = rt::launch_finalize_f64(a, sub, st);
     if (e == hipSuccess && ps) e = hipEventRecord(ps->e1, st);
     if (e == hipSuccess && ps) e = hipMemcpyAsync(ps->count, ws->counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     give_workspace(s, std::move(ws), st);
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("pixel-list render: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
     return RT_OK;
 }
 
@@ -2225,15 +2235,19 @@ int check_sparse(const char* who, const rt_accum* a, const void* pixels, int64_t
 }
 
 // Merges the compact pass d_sub of the device list d_pixels on `st` and waits for it; the first sparse merge fills the
-// per-pixel counts with the frame's (K, N).
+// per-pixel counts with the frame's (K, N). The merge launch is the varying part: one pass per pixel, or with d_counts
+// and d_off (device, n_pixels entries) the run merge of a batched pass, d_counts[e] passes of pixel e from unit d_off[e] on.
 int accum_merge_list(rt_accum* a, const uint32_t* d_pixels, int64_t n_pixels, const double* d_sub, int32_t n,
-                     hipStream_t st) {
+                     hipStream_t st, const uint8_t* d_counts = nullptr, const uint32_t* d_off = nullptr) {
     hipError_t e = hipSuccess;
     if (!a->sparse) e = rt::launch_accum_cnt_fill(a->cnt(), (long)a->npix(), (uint32_t)a->K, (uint32_t)a->N, false, st);
-    if (e == hipSuccess) e = rt::launch_accum_add_list(a->S, a->Q, a->cnt(), d_pixels, (long)n_pixels, d_sub, n, st);
+    if (e == hipSuccess)
+        e = d_counts ? rt::launch_accum_add_runs(a->S, a->Q, a->cnt(), d_pixels, d_counts, d_off, (long)n_pixels, d_sub, n, st)
+                     : rt::launch_accum_add_list(a->S, a->Q, a->cnt(), d_pixels, (long)n_pixels, d_sub, n, st);
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum sparse merge: ") + hipGetErrorString(e));
+    if (e != hipSuccess)
+        return fail(RT_E_HIP, std::string(d_counts ? "rt_accum run merge: " : "rt_accum sparse merge: ") + hipGetErrorString(e));
     a->sparse = true;
     return RT_OK;
 }
@@ -2298,17 +2312,14 @@ int rt_render_pixels_with_device(const rt_scene* scene, const rt_render_params* 
     int family;
     if (rc == RT_OK) rc = list_family_of("rt_render_pixels_device", scene, params, n_pixels, path, &family);
     if (rc != RT_OK) return rc;
-    if (n_pixels == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
+    if (n_pixels == 0) return empty_list(stats);
     rc = need_device("rt_render_pixels_device", params->device);
     if (rc != RT_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     PendingStats ps;
     ps.out = stats;
-    rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), params, (const uint32_t*)d_pixels, n_pixels, (uint8_t*)d_rgb,
-                               (double*)d_sub, st, nullptr, stats ? &ps : nullptr, path);
+    rc = render_units_enqueue(const_cast<rt_scene*>(scene), params, {(const uint32_t*)d_pixels, n_pixels, nullptr},
+                              (uint8_t*)d_rgb, (double*)d_sub, st, nullptr, stats ? &ps : nullptr, path, kListRender);
     return stats_sync(rc, st, stats ? &ps : nullptr);
 }
 
@@ -2325,10 +2336,7 @@ int rt_render_pixels_with(const rt_scene* scene, const rt_render_params* p, cons
     int family;
     if (rc == RT_OK) rc = list_family_of("rt_render_pixels", scene, p, n_pixels, path, &family);
     if (rc != RT_OK) return rc;
-    if (n_pixels == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
+    if (n_pixels == 0) return empty_list(stats);
     rc = need_device("rt_render_pixels", p->device);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
@@ -2342,8 +2350,8 @@ int rt_render_pixels_with(const rt_scene* scene, const rt_render_params* p, cons
     uint8_t* d_rgb = call.mem.at<uint8_t>(at_rgb);
     const hipError_t e = hipMemcpyAsync(d_pix, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, call.cs.st);
     if (e != hipSuccess) return oom_or_hip(e, "rt_render_pixels");
-    rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), p, d_pix, n_pixels, rgb_out ? d_rgb : nullptr, d_sub,
-                               call.cs.st, call.mirror.dev, &call.ps, path);
+    rc = render_units_enqueue(const_cast<rt_scene*>(scene), p, {d_pix, n_pixels, nullptr}, rgb_out ? d_rgb : nullptr, d_sub,
+                              call.cs.st, call.mirror.dev, &call.ps, path, kListRender);
     return call.finish("rt_render_pixels", rc, {{rgb_out, d_rgb, n * 3}, {sub_out, d_sub, b_sub}});
 }
 
@@ -2369,10 +2377,7 @@ int rt_accum_add_pixels(void* accum, const rt_scene* scene, const rt_render_para
     if (rc == RT_OK) rc = check_render_pixels("rt_accum_add_pixels", scene, p, pixels, n_pixels);
     if (rc == RT_OK) rc = check_sparse("rt_accum_add_pixels", a, pixels, n_pixels, true);
     if (rc != RT_OK) return rc;
-    if (n_pixels == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
+    if (n_pixels == 0) return empty_list(stats);
     rc = accum_ready("rt_accum_add_pixels", a, true, true);
     if (rc != RT_OK) return rc;
     RenderCall call;
@@ -2381,8 +2386,8 @@ int rt_accum_add_pixels(void* accum, const rt_scene* scene, const rt_render_para
     hipStream_t st = call.cs.st;
     const hipError_t e = hipMemcpyAsync(adapt_list(a), pixels, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return oom_or_hip(e, "rt_accum_add_pixels");
-    rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), p, adapt_list(a), n_pixels, nullptr, a->stage_sub(), st,
-                               call.mirror.dev, &call.ps);
+    rc = render_units_enqueue(const_cast<rt_scene*>(scene), p, {adapt_list(a), n_pixels, nullptr}, nullptr, a->stage_sub(),
+                              st, call.mirror.dev, &call.ps, RT_LIST_AUTO, kListRender);
     rc = call.finish("rt_accum_add_pixels", rc);
     if (rc != RT_OK) return rc;  // failed, or cancelled: nothing merged
     return accum_merge_list(a, adapt_list(a), n_pixels, a->stage_sub(), p->spp / 4, st);
@@ -2619,8 +2624,8 @@ int rt_accum_fill(void* accum, const rt_scene* scene, const rt_render_params* p,
         if (n_list > (int64_t)INT32_MAX / 4) return fail(RT_E_INVAL, "rt_accum_fill: the list's length * 4 must fit an int32");
         rt_render_params pp = *p;
         if (pass == 1) pp.seed = seed2;
-        rc = render_pixels_enqueue(const_cast<rt_scene*>(scene), &pp, adapt_list(a), n_list, nullptr, a->stage_sub(), st,
-                                   call.mirror.dev, &call.ps);
+        rc = render_units_enqueue(const_cast<rt_scene*>(scene), &pp, {adapt_list(a), n_list, nullptr}, nullptr,
+                                  a->stage_sub(), st, call.mirror.dev, &call.ps, RT_LIST_AUTO, kListRender);
         rc = call.finish("rt_accum_fill", rc);
         if (rc < 0) return rc;
         if (rc != RT_OK) break;  // cancelled: this pass merges nothing and the accumulator stays uncovered
@@ -2718,61 +2723,6 @@ hipError_t seeds_upload(uint64_t* d_seeds, const uint64_t* seeds, int32_t n_seed
     return hipMemcpyAsync(d_seeds, h16, RT_PASSES_MAX * sizeof(uint64_t), hipMemcpyHostToDevice, st);
 }
 
-// render_pixels_enqueue for unit words (the passes kernel of `path`'s family + k_finalize_f64 on the compact buffer):
-// n_units > 0 device words and 16 device seeds; arguments checked by check_passes (and list_family_of for a path other
-// than RT_LIST_AUTO: the family rule is the pixel list's). d_rgb and d_sub may be null.
-int render_passes_enqueue(rt_scene* s, const rt_render_params* p, const uint32_t* d_units, int64_t n_units,
-                          const uint64_t* d_seeds, uint8_t* d_rgb, double* d_sub, hipStream_t st, const int32_t* dcancel,
-                          PendingStats* ps, int32_t path = RT_LIST_AUTO) {
-    int family = RT_LIST_FUSED;
-    int rc = list_family_of("batched render", s, p, n_units, path, &family);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    rt::DevScene ds;
-    rc = upload(s, p->device, &ds);
-    if (rc != RT_OK) return rc;
-    rt::RenderArgs a = make_render_args(s, p, ds);
-    a.x0 = 0;
-    a.y0 = 0;
-    a.row_step = 1;
-    a.tw = (int32_t)n_units;  // k_finalize_f64's view of the compact buffer
-    a.th = 1;
-    a.seed = 0;  // unused: every unit draws from its pass's seed
-    a.rgb_out = d_rgb;
-    a.cancel = dcancel;
-    if (ps) {
-        const hipError_t e = ps->init(ps->out);
-        if (e != hipSuccess) return fail(RT_E_HIP, std::string("stats: ") + hipGetErrorString(e));
-        ps->samples = n_units * 4 * (int64_t)a.n_samples;
-        HIP_TRY(hipEventRecord(ps->e0, st));
-    }
-    hipError_t te;
-    std::unique_ptr<rt::Workspace> ws = take_workspace(s, p->device, st, &te);
-    if (!ws) return fail(RT_E_HIP, std::string("workspace: ") + hipGetErrorString(te));
-    hipError_t e = ws->ensure_counters();
-    double* sub = d_sub;
-    if (e == hipSuccess && !sub) {
-        e = ws->ensure_sub((size_t)n_units);
-        sub = ws->sub_buf;
-    }
-    a.sub_out = sub;
-    if (e == hipSuccess && ps) e = hipMemsetAsync(ws->counters, 0, 8 * sizeof(unsigned long long), st);
-    if (e == hipSuccess && a.n_samples <= 0) e = hipMemsetAsync(sub, 0, (size_t)n_units * 12 * sizeof(double), st);
-    if (e == hipSuccess) {
-        a.counters = ps ? ws->counters : nullptr;
-        // the pool kernels split their last units into chunks of samples: the frame's scratch rule, for this many units
-        if (family != RT_LIST_FUSED) ensure_tail_scratch(ws.get(), a, (size_t)n_units);
-        e = rt::launch_render_passes_f64(ds, a, d_units, (long)n_units, d_seeds, sub, (uint32_t*)(ws->counters + 4), family,
-                                         ws->tail_buf, ws->tail_cap, st);
-    }
-    if (e == hipSuccess && d_rgb) e = rt::launch_finalize_f64(a, sub, st);
-    if (e == hipSuccess && ps) e = hipEventRecord(ps->e1, st);
-    if (e == hipSuccess && ps) e = hipMemcpyAsync(ps->count, ws->counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-    give_workspace(s, std::move(ws), st);
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("batched render: ") + hipGetErrorString(e));
-    return RT_OK;
-}
-
 int check_plan(const char* who, const rt_accum* a, float abs_tol, float rel_tol, int32_t n, float gain,
                int32_t max_passes) {
     const std::string w(who);
@@ -2830,20 +2780,6 @@ int plan_run(const char* who, rt_accum* a, float abs_tol, float rel_tol, int32_t
     return RT_OK;
 }
 
-// The run merge of the device lists on `st`, waited for; the first sparse merge fills the per-pixel counts.
-int accum_merge_runs(rt_accum* a, const uint32_t* d_pixels, const uint8_t* d_counts, const uint32_t* d_off,
-                     int64_t n_pixels, const double* d_sub, int32_t n, hipStream_t st) {
-    hipError_t e = hipSuccess;
-    if (!a->sparse) e = rt::launch_accum_cnt_fill(a->cnt(), (long)a->npix(), (uint32_t)a->K, (uint32_t)a->N, false, st);
-    if (e == hipSuccess)
-        e = rt::launch_accum_add_runs(a->S, a->Q, a->cnt(), d_pixels, d_counts, d_off, (long)n_pixels, d_sub, n, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_accum run merge: ") + hipGetErrorString(e));
-    a->sparse = true;
-    return RT_OK;
-}
-
 // Expands the accumulator's device lists (adapt_list, batch_counts: n_pixels entries, `units` units in all), renders
 // the units into the staging buffer with the 16 seeds in batch_seeds and merges them; RT_CANCELLED merges nothing.
 int batch_render_merge(const char* who, rt_accum* a, const rt_scene* scene, const rt_render_params* p, int64_t n_pixels,
@@ -2853,11 +2789,11 @@ int batch_render_merge(const char* who, rt_accum* a, const rt_scene* scene, cons
                                                  batch_units(a), (long)units, batch_words(a) + 20, st);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
     // RT_LIST_AUTO: the scene's pool wherever it has one
-    int rc = render_passes_enqueue(const_cast<rt_scene*>(scene), p, batch_units(a), units, batch_seeds(a), nullptr,
-                                   a->stage_sub(), st, call.mirror.dev, &call.ps);
+    int rc = render_units_enqueue(const_cast<rt_scene*>(scene), p, {batch_units(a), units, batch_seeds(a)}, nullptr,
+                                  a->stage_sub(), st, call.mirror.dev, &call.ps, RT_LIST_AUTO, kBatchRender);
     rc = call.finish(who, rc);
     if (rc != RT_OK) return rc;  // failed, or cancelled: nothing merged
-    return accum_merge_runs(a, adapt_list(a), batch_counts(a), batch_off(a), n_pixels, a->stage_sub(), p->spp / 4, st);
+    return accum_merge_list(a, adapt_list(a), n_pixels, a->stage_sub(), p->spp / 4, st, batch_counts(a), batch_off(a));
 }
 
 }  // namespace
@@ -2873,10 +2809,7 @@ int rt_render_pixel_passes_with(const rt_scene* scene, const rt_render_params* p
     int family;
     if (rc == RT_OK) rc = list_family_of(who, scene, p, units, path, &family);
     if (rc != RT_OK) return rc;
-    if (n_pixels == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
+    if (n_pixels == 0) return empty_list(stats);
     rc = need_device(who, p->device);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
@@ -2901,8 +2834,8 @@ int rt_render_pixel_passes_with(const rt_scene* scene, const rt_render_params* p
     hipError_t e = hipMemcpyAsync(d_units, words.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, call.cs.st);
     if (e == hipSuccess) e = seeds_upload(d_seeds, seeds, n_seeds, h_seeds, call.cs.st);
     if (e != hipSuccess) return oom_or_hip(e, who);
-    rc = render_passes_enqueue(const_cast<rt_scene*>(scene), p, d_units, units, d_seeds, rgb_out ? d_rgb : nullptr, d_sub,
-                               call.cs.st, call.mirror.dev, &call.ps, path);
+    rc = render_units_enqueue(const_cast<rt_scene*>(scene), p, {d_units, units, d_seeds}, rgb_out ? d_rgb : nullptr, d_sub,
+                              call.cs.st, call.mirror.dev, &call.ps, path, kBatchRender);
     return call.finish(who, rc, {{rgb_out, d_rgb, n * 3}, {sub_out, d_sub, b_sub}});
 }
 
@@ -2924,10 +2857,7 @@ int rt_render_pixel_passes_with_device(const rt_scene* scene, const rt_render_pa
     int family;
     if (rc == RT_OK) rc = list_family_of(who, scene, p, units, path, &family);
     if (rc != RT_OK) return rc;
-    if (n_pixels == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
+    if (n_pixels == 0) return empty_list(stats);
     rc = need_device(who, p->device);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipSetDevice(p->device));
@@ -2946,8 +2876,8 @@ int rt_render_pixel_passes_with_device(const rt_scene* scene, const rt_render_pa
                                     nullptr, mem.at<uint32_t>(at_units), (long)units, mem.at<uint32_t>(at_total), st);
     if (e != hipSuccess) rc = fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
     if (rc == RT_OK)
-        rc = render_passes_enqueue(const_cast<rt_scene*>(scene), p, mem.at<uint32_t>(at_units), units, mem.at<uint64_t>(at_seeds),
-                                   (uint8_t*)d_rgb, (double*)d_sub, st, nullptr, stats ? &ps : nullptr, path);
+        rc = render_units_enqueue(const_cast<rt_scene*>(scene), p, {mem.at<uint32_t>(at_units), units, mem.at<uint64_t>(at_seeds)},
+                                  (uint8_t*)d_rgb, (double*)d_sub, st, nullptr, stats ? &ps : nullptr, path, kBatchRender);
     // the call's scratch lives until the render is done: this form always waits
     e = hipStreamSynchronize(st);
     if (rc == RT_OK && e != hipSuccess) rc = fail(RT_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
@@ -3022,10 +2952,7 @@ int rt_accum_add_passes(void* accum, const rt_scene* scene, const rt_render_para
     if (rc == RT_OK) rc = check_pass_counts(who, counts, n_pixels, n_seeds, (int64_t)a->npix(), &units);
     if (rc == RT_OK) rc = check_sparse(who, a, pixels, n_pixels, false);  // (K >= 2, asked for last)
     if (rc != RT_OK) return rc;
-    if (n_pixels == 0) {
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
+    if (n_pixels == 0) return empty_list(stats);
     rc = batch_ready(who, a);
     if (rc != RT_OK) return rc;
     uint64_t h_seeds[RT_PASSES_MAX];
@@ -3065,10 +2992,7 @@ int rt_accum_refine(void* accum, const rt_scene* scene, const rt_render_params* 
         out[1] = res[1];
         out[2] = res[2];
     }
-    if (res[0] == 0) {  // an empty plan launches nothing
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
-    }
+    if (res[0] == 0) return empty_list(stats);  // an empty plan launches nothing
     const hipError_t e = seeds_upload(batch_seeds(a), seeds, n_seeds, h_seeds, st);
     if (e != hipSuccess) return oom_or_hip(e, who);
     return batch_render_merge(who, a, scene, p, res[0], res[1], call);
