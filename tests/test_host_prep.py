@@ -335,7 +335,7 @@ def test_root_order_grid_form_matches_insertion_sort():
 
 def _speck_toml(tmp_path, n=64):
     """A mesh far smaller than its own cull padding: n triangles inside a 1e-8 cube at (1e6, 1e6, 1e6), whose
-    cull padding is 1e-7 * 1e6 = 0.1 (rt_api.cpp pack_scene)."""
+    cull padding is 1e-7 * 1e6 = 0.1 (scene_pack.cpp pack_scene)."""
     rng = np.random.default_rng(3)
     lines = []
     for t in range(n):
@@ -360,7 +360,7 @@ geometry = { type = "sphere", pos = [50.0, 70.0, 100.0], r = 4.0 }
 
 
 def test_slot_bound_codes_never_clamp_on_reference_meshes(rt, tmp_path):
-    """rt_api.cpp make_slot: the walks decode every subtree-bound code as base + q * step (path_f64.h
+    """scene_pack.cpp make_slot: the walks decode every subtree-bound code as base + q * step (path_f64.h
     tight_lo / tight_hi), which encloses the subtree only if no code was clamped to the 16-bit range, so a
     scene keeps its slot tables only then. The reference meshes keep them (their codes lie in about
     [E / step, 2 E / step]); a mesh smaller than its own cull padding (1e-7 of its coordinates' scale), far
