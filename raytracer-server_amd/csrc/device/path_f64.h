@@ -1521,9 +1521,13 @@ struct Cfg {
     static constexpr bool nospec = (F & 32) != 0;  // no specular (mirror) object: the mirror paths compile out
     static constexpr bool ldsobj = (F & 64) != 0;  // the kernel holds the object table in LDS (rt_lds_objects)
     static constexpr bool g1 = (F & 128) != 0;     // the one-ballot guards (rcp_safe_all's G1): the fused mesh instances
+    static constexpr bool tabuse = (F & 256) != 0;  // compact tables read at each use, not in batches (kCfgTabUse)
 };
 constexpr int kCfgLdsObj = 64;
 constexpr int kCfgGuards1 = 128;
+// The compact tables read operand by operand at each use instead of in batches (below: tables_form): for an
+// instance whose registers or spills would grow with the batch windows.
+constexpr int kCfgTabUse = 256;
 
 // The object table of compact scenes in LDS (16 x 208 B): a megakernel instantiated with Cfg bit 64
 // copies DevScene::objects here at its start (lds_objects_fill), so the shading's per-lane object reads
@@ -1546,6 +1550,9 @@ RT_DEV void lds_objects_fill(const DevScene& sc) {
 // Per-call view of the compact tables (scene_layout.h: CompactTab). The empty asm makes the pointer
 // opaque, so the scalar loads through it are issued inside each trace call instead of being
 // hoisted to the kernel entry, where the tables would hold ~100 SGPRs across the path loop.
+// Inside a call the loops read a group's operands (the four counts; one axis' positions and indices; one
+// sphere row) as one batch of wide scalar loads issued ahead of the arithmetic before the group, and hold it
+// only across that group (AxisBatch / spheres_batched below); Cfg::tabuse keeps one load per operand at its use.
 // kSext = true is the round-4 first build's reconstruction, in which the builtin's int result of the low
 // word sign-extended into the high word (an illegal address whenever hipMalloc placed the table at a low
 // word with bit 31 set: profiles/r04_ab.log). Only rt_selftest_tables instantiates it, to show that its
@@ -1565,6 +1572,62 @@ RT_DEV CTab* tables_form(const DevScene& sc) {
     return (CTab*)p;
 }
 RT_DEV CTab* tables(const DevScene& sc) { return tables_form<false>(sc); }
+
+// ---- operand sources of the compact loops (axis_planes, planes_clear, the sphere loops) ----
+// The arrays of CompactTab have fixed sizes and the packer zeroes unused slots (scene_pack.cpp: the memset in
+// front of fill_compact), so a batch reads whole arrays unconditionally and in bounds; the loops keep their
+// scalar `i < n` guards, so an unused slot's value is never an operand. The wide loads need 4-byte alignment only.
+typedef int32_t TabI4 __attribute__((ext_vector_type(4)));
+typedef double TabD4 __attribute__((ext_vector_type(4)));
+typedef TabI4 TabI4A __attribute__((aligned(4)));
+typedef TabD4 TabD4A __attribute__((aligned(8)));
+typedef const __attribute__((address_space(4))) int32_t* CTabPtrI;
+typedef const __attribute__((address_space(4))) double* CTabPtrD;
+RT_DEV TabI4 tab_i4(CTabPtrI p) { return *(const __attribute__((address_space(4))) TabI4A*)p; }
+RT_DEV TabD4 tab_d4(CTabPtrD p) { return *(const __attribute__((address_space(4))) TabD4A*)p; }
+// Keeps a batch where it was issued: the values pass through one empty asm placed after the arithmetic that
+// covers their latency (one wait for the whole batch), so the loads cannot sink into the guarded blocks that
+// use them (tables_form's idiom).
+template <class A>
+RT_DEV void tab_hold(A& a) { asm volatile("" : "+s"(a)); }
+template <class A, class B>
+RT_DEV void tab_hold(A& a, B& b) { asm volatile("" : "+s"(a), "+s"(b)); }
+template <class A, class B, class C>
+RT_DEV void tab_hold(A& a, B& b, C& c) { asm volatile("" : "+s"(a), "+s"(b), "+s"(c)); }
+template <class A, class B, class C, class D>
+RT_DEV void tab_hold(A& a, B& b, C& c, D& d) { asm volatile("" : "+s"(a), "+s"(b), "+s"(c), "+s"(d)); }
+// The table pointer made opaque again: a second read of an operand stays a load of its own at its place
+// instead of extending the first read's registers to it.
+RT_DEV CTab* tab_again(CTab* T) {
+    uint64_t p = (uint64_t)T;
+    asm volatile("" : "+s"(p));
+    return (CTab*)p;
+}
+
+// n_ax[0..2] and n_sph: the counts every compact query reads
+RT_DEV TabI4 tab_counts(CTab* T) { return tab_i4(&T->n_ax[0]); }
+// Axis K's batch: its kMaxAxisPlanes positions and (Idx) object indices, 8 or 12 SGPRs
+template <bool Idx>
+struct AxisBatch {
+    TabD4 p;
+    TabI4 x;
+    RT_DEV double pos(int i) const { return p[i]; }
+    RT_DEV int idx(int i) const { return Idx ? x[i] : -1; }
+    RT_DEV void hold() {
+        if constexpr (Idx) tab_hold(p, x);
+        else tab_hold(p);
+    }
+};
+template <int K, bool Idx>
+RT_DEV AxisBatch<Idx> axis_fetch(CTab* T) {
+    static_assert(kMaxAxisPlanes == 4, "one TabD4 / TabI4 per axis");
+    AxisBatch<Idx> a;
+    a.p = tab_d4(&T->ax_pos[K][0]);
+    if constexpr (Idx) a.x = tab_i4(&T->ax_idx[K][0]);
+    return a;
+}
+// One sphere row (centre xyz, r*r), 8 SGPRs: sphere_c's operand
+RT_DEV TabD4 sph_fetch(CTab* T, int i) { return tab_d4(&T->sph[i][0]); }
 
 // One object's Geometry::intersect, reporting t (and the triangle for meshes).
 template <class C>
@@ -1629,6 +1692,60 @@ RT_DEV void axis_planes(const DevScene& sc, CTab* T, const Ray& ray, const RayIn
         }
     }
 }
+// The same on axis K's batch `a` and its count n
+template <int K, bool Idx, class Visit>
+RT_DEV void axis_group(int n, const AxisBatch<Idx>& a, const Ray& ray, const RayInv& inv, Visit&& visit) {
+    if (n == 0) return;
+    const double dk = K == 0 ? ray.d.x : K == 1 ? ray.d.y : ray.d.z;
+    if (fabs(dk) < 0.0001) return;
+    const double ok = K == 0 ? ray.o.x : K == 1 ? ray.o.y : ray.o.z;
+#pragma unroll
+    for (int i = 0; i < kMaxAxisPlanes; ++i) {
+        if (i < n) {
+            double num = a.pos(i) - ok;
+            double t = K == 0 ? div_x(num, ray, inv) : K == 1 ? div_y(num, ray, inv) : div_z(num, ray, inv);
+            if (t >= 0.) visit(t, a.idx(i), -1);
+        }
+    }
+}
+// The sphere loop on batches: row 0 (and the indices sx, when Idx) was issued in front of the arithmetic before
+// this call; each later row is issued before the arithmetic of the sphere in front of it. f(t, object index)
+// per hit, in slot order.
+template <bool G1, bool Idx, class F>
+RT_DEV void spheres_batched(CTab* T, int n, TabD4& r0, TabI4& sx, const Ray& ray, F&& f) {
+    static_assert(kMaxSpheres == 4, "rows 0..3");
+    if constexpr (Idx) tab_hold(r0, sx);
+    else tab_hold(r0);
+    double t;
+    TabD4 r1 = sph_fetch(T, 1);
+    if (0 < n && sphere_c<G1>(r0, ray, &t)) f(t, Idx ? sx[0] : -1);
+    tab_hold(r1);
+    TabD4 r2 = sph_fetch(T, 2);
+    if (1 < n && sphere_c<G1>(r1, ray, &t)) f(t, Idx ? sx[1] : -1);
+    tab_hold(r2);
+    TabD4 r3 = sph_fetch(T, 3);
+    if (2 < n && sphere_c<G1>(r2, ray, &t)) f(t, Idx ? sx[2] : -1);
+    tab_hold(r3);
+    if (3 < n && sphere_c<G1>(r3, ray, &t)) f(t, Idx ? sx[3] : -1);
+}
+// The closest-hit query's axis planes and spheres on batches: cn and a0 were issued in front of the arithmetic
+// before this call (make_inv, where the caller has it); each later batch is issued before the arithmetic of the
+// group in front of its own, so a group waits once at most.
+template <bool G1>
+RT_DEV void closest_batched(CTab* T, TabI4& cn, AxisBatch<true>& a0, const Ray& ray, const RayInv& inv, HitRec& h) {
+    auto visit = [&](double t, int idx, int prim) { consider(h, t, idx, prim); };
+    tab_hold(cn, a0.p, a0.x);
+    AxisBatch<true> a1 = axis_fetch<1, true>(T);
+    axis_group<0>(cn[0], a0, ray, inv, visit);
+    a1.hold();
+    AxisBatch<true> a2 = axis_fetch<2, true>(T);
+    axis_group<1>(cn[1], a1, ray, inv, visit);
+    a2.hold();
+    TabD4 r0 = sph_fetch(T, 0);
+    TabI4 sx = tab_i4(&T->sph_idx[0]);
+    axis_group<2>(cn[2], a2, ray, inv, visit);
+    spheres_batched<G1, true>(T, cn[3], r0, sx, ray, [&](double t, int idx) { consider(h, t, idx, -1); });
+}
 
 template <class C>
 RT_DEV HitRec trace_closest(const DevScene& sc, const Ray& ray) {
@@ -1636,20 +1753,31 @@ RT_DEV HitRec trace_closest(const DevScene& sc, const Ray& ray) {
     CTab* T = tables(sc);
     HitRec h{0.0, -1, -1};
     RT_DBG_TSTART(t_pl);
+    TabI4 cn;
+    AxisBatch<true> a0;
+    if constexpr (C::compact && !C::tabuse) {  // the counts and axis 0's batch in flight across make_inv
+        cn = tab_counts(T);
+        a0 = axis_fetch<0, true>(T);
+    }
     const RayInv inv = make_inv<C::g1>(ray.d);
     if constexpr (C::compact) {
-        auto visit = [&](double t, int idx, int prim) { consider(h, t, idx, prim); };
-        axis_planes<0>(sc, T, ray, inv, visit);
-        axis_planes<1>(sc, T, ray, inv, visit);
-        axis_planes<2>(sc, T, ray, inv, visit);
-        RT_DBG_TEND(13, t_pl);
-        RT_DBG_TSTART(t_sp);
+        if constexpr (C::tabuse) {
+            auto visit = [&](double t, int idx, int prim) { consider(h, t, idx, prim); };
+            axis_planes<0>(sc, T, ray, inv, visit);
+            axis_planes<1>(sc, T, ray, inv, visit);
+            axis_planes<2>(sc, T, ray, inv, visit);
+            RT_DBG_TEND(13, t_pl);
+            RT_DBG_TSTART(t_sp);
 #pragma unroll
-        for (int i = 0; i < kMaxSpheres; ++i) {
-            double t;
-            if (i < T->n_sph && sphere_c<C::g1>(T->sph[i], ray, &t)) consider(h, t, T->sph_idx[i], -1);
+            for (int i = 0; i < kMaxSpheres; ++i) {
+                double t;
+                if (i < T->n_sph && sphere_c<C::g1>(T->sph[i], ray, &t)) consider(h, t, T->sph_idx[i], -1);
+            }
+            RT_DBG_TEND(14, t_sp);
+        } else {
+            closest_batched<C::g1>(T, cn, a0, ray, inv, h);
+            RT_DBG_TEND(13, t_pl);
         }
-        RT_DBG_TEND(14, t_sp);
         for (int i = 0; i < T->n_gen; ++i) {
             const int idx = T->gen_idx[i];
             double t;
@@ -1714,6 +1842,50 @@ RT_DEV bool planes_clear(CTab* T, double xk, double yk) {
     }
     return c;
 }
+// The same on an axis' batch `a` and its count n
+RT_DEV bool group_clear(int n, const AxisBatch<false>& a, double xk, double yk) {
+    bool c = true;
+#pragma unroll
+    for (int i = 0; i < kMaxAxisPlanes; ++i) {
+        if (i < n) {
+            const double p = a.pos(i);
+            c &= (xk < p && yk < p) || (xk > p && yk > p);
+        }
+    }
+    return c;
+}
+// The shadow query's axis planes and spheres on batches: the counts and every plane position in one group of
+// loads, the first sphere row issued before the last axis' clear test. The exact plane tests (lanes whose
+// segment crosses or touches a plane: none in most waves) read their axis again, one batch each. Returns
+// "occluded"; inv is made here where the planes need it and `have_inv` says the caller did not.
+template <bool G1>
+RT_DEV bool shadow_batched(CTab* T, V3 y, const Ray& r, double dist, RayInv& inv, bool have_inv) {
+    const double ERR_MARGIN = 0.001;
+    bool occluded = false;
+    auto visit = [&](double t, int, int) { occluded |= !(t + ERR_MARGIN >= dist); };
+    TabI4 cn = tab_counts(T);
+    AxisBatch<false> a0 = axis_fetch<0, false>(T), a1 = axis_fetch<1, false>(T), a2 = axis_fetch<2, false>(T);
+    tab_hold(cn, a0.p, a1.p, a2.p);
+    bool clear = dist < 1e9 && group_clear(cn[0], a0, r.o.x, y.x) && group_clear(cn[1], a1, r.o.y, y.y);
+    TabD4 r0 = sph_fetch(T, 0);
+    clear = clear && group_clear(cn[2], a2, r.o.z, y.z);
+    if (!clear) {
+        if (!have_inv) inv = make_inv<G1>(r.d);
+        CTab* T2 = tab_again(T);
+        AxisBatch<false> b0 = axis_fetch<0, false>(T2);
+        b0.hold();
+        axis_group<0>(cn[0], b0, r, inv, visit);
+        AxisBatch<false> b1 = axis_fetch<1, false>(T2);
+        b1.hold();
+        axis_group<1>(cn[1], b1, r, inv, visit);
+        AxisBatch<false> b2 = axis_fetch<2, false>(T2);
+        b2.hold();
+        axis_group<2>(cn[2], b2, r, inv, visit);
+    }
+    TabI4 none;
+    spheres_batched<G1, false>(T, cn[3], r0, none, r, [&](double t, int) { occluded |= !(t + ERR_MARGIN >= dist); });
+    return occluded;
+}
 template <class C>
 RT_DEV bool visible_ray(const DevScene& sc, V3 y, const Ray& r, double dist) {
     RT_DBG_REGION(13);
@@ -1721,22 +1893,28 @@ RT_DEV bool visible_ray(const DevScene& sc, V3 y, const Ray& r, double dist) {
     const double ERR_MARGIN = 0.001;
     if constexpr (C::compact) {
         bool occluded = false;
-        auto visit = [&](double t, int, int) { occluded |= !(t + ERR_MARGIN >= dist); };
-        const bool clear = dist < 1e9 && planes_clear<0>(T, r.o.x, y.x) && planes_clear<1>(T, r.o.y, y.y) &&
-                           planes_clear<2>(T, r.o.z, y.z);
         RayInv inv;
-        const bool gen = T->n_gen > 0;  // the generic intersectors use the reciprocals too
-        if (gen) inv = make_inv<C::g1>(r.d);
-        if (!clear) {
-            if (!gen) inv = make_inv<C::g1>(r.d);
-            axis_planes<0>(sc, T, r, inv, visit);
-            axis_planes<1>(sc, T, r, inv, visit);
-            axis_planes<2>(sc, T, r, inv, visit);
-        }
+        if constexpr (C::tabuse) {
+            auto visit = [&](double t, int, int) { occluded |= !(t + ERR_MARGIN >= dist); };
+            const bool clear = dist < 1e9 && planes_clear<0>(T, r.o.x, y.x) && planes_clear<1>(T, r.o.y, y.y) &&
+                               planes_clear<2>(T, r.o.z, y.z);
+            const bool gen = T->n_gen > 0;  // the generic intersectors use the reciprocals too
+            if (gen) inv = make_inv<C::g1>(r.d);
+            if (!clear) {
+                if (!gen) inv = make_inv<C::g1>(r.d);
+                axis_planes<0>(sc, T, r, inv, visit);
+                axis_planes<1>(sc, T, r, inv, visit);
+                axis_planes<2>(sc, T, r, inv, visit);
+            }
 #pragma unroll
-        for (int i = 0; i < kMaxSpheres; ++i) {
-            double t;
-            if (i < T->n_sph && sphere_c<C::g1>(T->sph[i], r, &t)) occluded |= !(t + ERR_MARGIN >= dist);
+            for (int i = 0; i < kMaxSpheres; ++i) {
+                double t;
+                if (i < T->n_sph && sphere_c<C::g1>(T->sph[i], r, &t)) occluded |= !(t + ERR_MARGIN >= dist);
+            }
+        } else {
+            const bool gen = T->n_gen > 0;  // the generic intersectors use the reciprocals too
+            if (gen) inv = make_inv<C::g1>(r.d);
+            occluded = shadow_batched<C::g1>(T, y, r, dist, inv, gen);
         }
         if (occluded) return false;
         for (int i = 0; i < T->n_gen; ++i) {
@@ -1774,14 +1952,20 @@ template <class C>
 RT_DEV HitRec trace_analytic(const DevScene& sc, const Ray& ray, const RayInv& inv) {
     CTab* T = tables(sc);
     HitRec h{0.0, -1, -1};
-    auto visit = [&](double t, int idx, int prim) { consider(h, t, idx, prim); };
-    axis_planes<0>(sc, T, ray, inv, visit);
-    axis_planes<1>(sc, T, ray, inv, visit);
-    axis_planes<2>(sc, T, ray, inv, visit);
+    if constexpr (C::tabuse) {
+        auto visit = [&](double t, int idx, int prim) { consider(h, t, idx, prim); };
+        axis_planes<0>(sc, T, ray, inv, visit);
+        axis_planes<1>(sc, T, ray, inv, visit);
+        axis_planes<2>(sc, T, ray, inv, visit);
 #pragma unroll
-    for (int i = 0; i < kMaxSpheres; ++i) {
-        double t;
-        if (i < T->n_sph && sphere_c(T->sph[i], ray, &t)) consider(h, t, T->sph_idx[i], -1);
+        for (int i = 0; i < kMaxSpheres; ++i) {
+            double t;
+            if (i < T->n_sph && sphere_c(T->sph[i], ray, &t)) consider(h, t, T->sph_idx[i], -1);
+        }
+    } else {
+        TabI4 cn = tab_counts(T);
+        AxisBatch<true> a0 = axis_fetch<0, true>(T);
+        closest_batched<false>(T, cn, a0, ray, inv, h);
     }
     for (int i = 0; i < T->n_gen; ++i) {
         if (!((T->gen_analytic >> i) & 1u)) continue;  // a mesh: analytic_t cannot hit it
@@ -1869,21 +2053,26 @@ RT_DEV bool visible_analytic(const DevScene& sc, V3 y, const Ray& r, double dist
     CTab* T = tables(sc);
     const double ERR_MARGIN = 0.001;
     bool occluded = false;
-    auto visit = [&](double t, int, int) { occluded |= !(t + ERR_MARGIN >= dist); };
-    const bool clear = dist < 1e9 && planes_clear<0>(T, r.o.x, y.x) && planes_clear<1>(T, r.o.y, y.y) &&
-                       planes_clear<2>(T, r.o.z, y.z);
     // the ray reciprocals only where they are used (make_inv's wave vote makes it a convergent call
     // the compiler cannot sink into these branches itself; its result is the same bits either way)
-    if (!clear) {
-        const RayInv inv = make_inv(r.d);
-        axis_planes<0>(sc, T, r, inv, visit);
-        axis_planes<1>(sc, T, r, inv, visit);
-        axis_planes<2>(sc, T, r, inv, visit);
-    }
+    if constexpr (C::tabuse) {
+        auto visit = [&](double t, int, int) { occluded |= !(t + ERR_MARGIN >= dist); };
+        const bool clear = dist < 1e9 && planes_clear<0>(T, r.o.x, y.x) && planes_clear<1>(T, r.o.y, y.y) &&
+                           planes_clear<2>(T, r.o.z, y.z);
+        if (!clear) {
+            const RayInv inv = make_inv(r.d);
+            axis_planes<0>(sc, T, r, inv, visit);
+            axis_planes<1>(sc, T, r, inv, visit);
+            axis_planes<2>(sc, T, r, inv, visit);
+        }
 #pragma unroll
-    for (int i = 0; i < kMaxSpheres; ++i) {
-        double t;
-        if (i < T->n_sph && sphere_c(T->sph[i], r, &t)) occluded |= !(t + ERR_MARGIN >= dist);
+        for (int i = 0; i < kMaxSpheres; ++i) {
+            double t;
+            if (i < T->n_sph && sphere_c(T->sph[i], r, &t)) occluded |= !(t + ERR_MARGIN >= dist);
+        }
+    } else {
+        RayInv inv;
+        occluded = shadow_batched<false>(T, y, r, dist, inv, false);
     }
     if (occluded) return false;
     if (T->gen_analytic) {

@@ -145,9 +145,13 @@ constexpr int kMaxSpheres = 4;
 constexpr int kMaxGeneric = 8;     // meshes and non-axis planes
 constexpr int kMaxCompactObjects = 16;  // compact scenes also hold their object table in LDS (3.3 KB)
 // The compact tables live in device memory (part of the scene blob) and are read through a
-// constant-address-space pointer: scalar loads at each use, so they never occupy SGPRs across the
-// path loop (as kernel arguments they did, and the spilled SGPRs were reloaded with ~900 static
-// v_readlane instructions in the cornell megakernel).
+// constant-address-space pointer: scalar loads inside each query, so they never occupy SGPRs across
+// the path loop (as kernel arguments they did, and the spilled SGPRs were reloaded with ~900 static
+// v_readlane instructions in the cornell megakernel). A query reads them a group at a time (path_f64.h
+// AxisBatch, spheres_batched): the counts n_ax[3], n_sph are 16 contiguous bytes, ax_idx[K] 16, ax_pos[K] 32,
+// sph_idx 16 and a sphere row 32, so a group is one or two wide loads, held in 8 to 12 SGPRs across that
+// group only. The arrays have fixed sizes and unused slots are zero (scene_pack.cpp), so a whole-array read
+// is in bounds and defined. The layout is pinned by tests/golden/scene_pack_tables.txt.
 struct CompactTab {
     int32_t n_ax[3];                         // planes with n = +-e_k, per axis k
     int32_t n_sph, n_gen;

@@ -90,7 +90,10 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
     // shading's per-lane object reads (hit object, light) are ds_reads instead of global loads.
     // the fused mesh instances (F odd) keep the one-ballot guards (path_f64.h kCfgGuards1: they sit at their
     // register cap, and the new guards raised their spill counts)
-    using C = Cfg<F | ((RT_OPT_LDSOBJ && (F & 8)) ? kCfgLdsObj : 0) | ((F & 1) ? kCfgGuards1 : 0)>;
+    // and, with the Phong + MIS mesh-free instance F = 14 (its pixel-list and batched-pass kernels), read the
+    // compact tables at each use (kCfgTabUse: the batch windows raised their spill counts)
+    using C = Cfg<F | ((RT_OPT_LDSOBJ && (F & 8)) ? kCfgLdsObj : 0) | ((F & 1) ? kCfgGuards1 | kCfgTabUse : 0) |
+                  (F == 14 ? kCfgTabUse : 0)>;
 #if RT_KARG_VIEW
     const DevScene& sc = karg_scene();  // the arguments read in place (megakernel_common.h)
     const RenderArgs& a = karg_render_args();
@@ -474,8 +477,8 @@ hipError_t launch_diag_fused(const DevScene& sc, const DiagArgs& a, bool visible
         case 2: hipLaunchKernelGGL(k_diag_fused<17>, grid, block, 0, st, sc, a, vis); break;
         case 3: hipLaunchKernelGGL(k_diag_fused<25>, grid, block, 0, st, sc, a, vis); break;
         case 4: hipLaunchKernelGGL(k_diag_fused<8>, grid, block, 0, st, sc, a, vis); break;
-        case 5: hipLaunchKernelGGL((k_diag_fused<9 | kCfgGuards1>), grid, block, 0, st, sc, a, vis); break;
-        default: hipLaunchKernelGGL((k_diag_fused<25 | kCfgGuards1>), grid, block, 0, st, sc, a, vis); break;
+        case 5: hipLaunchKernelGGL((k_diag_fused<9 | kCfgGuards1 | kCfgTabUse>), grid, block, 0, st, sc, a, vis); break;
+        default: hipLaunchKernelGGL((k_diag_fused<25 | kCfgGuards1 | kCfgTabUse>), grid, block, 0, st, sc, a, vis); break;
     }
     return hipGetLastError();
 }
@@ -525,13 +528,13 @@ hipError_t launch_diag_vertex_fused(const DevScene& sc, const RenderArgs& a, con
     } else if (guards == 1) {
         RT_DV_SWITCH(8, false)
     } else if (guards == 2) {
-        if (bvh) RT_DV_SWITCH(25 | kCfgGuards1, false) else RT_DV_SWITCH(9 | kCfgGuards1, false)
+        if (bvh) RT_DV_SWITCH(25 | kCfgGuards1 | kCfgTabUse, false) else RT_DV_SWITCH(9 | kCfgGuards1 | kCfgTabUse, false)
     } else if (!mesh) {  // fused_body's C: F | kCfgLdsObj for a compact scene, | kCfgGuards1 with meshes
         RT_DV_SWITCH(8 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0), RT_OPT_COLD != 0)
     } else if (bvh) {
-        RT_DV_SWITCH(25 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgGuards1, RT_OPT_COLD != 0)
+        RT_DV_SWITCH(25 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgGuards1 | kCfgTabUse, RT_OPT_COLD != 0)
     } else {
-        RT_DV_SWITCH(9 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgGuards1, RT_OPT_COLD != 0)
+        RT_DV_SWITCH(9 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgGuards1 | kCfgTabUse, RT_OPT_COLD != 0)
     }
 #undef RT_DV_SWITCH
 #undef RT_DV_CASE

@@ -312,7 +312,9 @@ RT_DEV void process_queries(const DevScene& sc, const int32_t* cnt_c, const int3
 template <int F, int W>
 __global__ __launch_bounds__(kBlk, W) void k_megakernel_flat_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                                 uint32_t* next_sub, long nsub) {
-    using C = Cfg<F | kCfgLdsObj>;  // the object table in LDS (path_f64.h rt_lds_objects)
+    // the object table in LDS (path_f64.h rt_lds_objects); the compact tables read at each use (kCfgTabUse: the
+    // batch windows raised the pool's SGPR spills)
+    using C = Cfg<F | kCfgLdsObj | kCfgTabUse>;
     static_assert(C::mesh && C::compact && !C::bvh, "flat-mesh kernel: compact scenes, octree meshes");
 #if RT_KARG_VIEW
     const DevScene& sc = karg_scene();  // the arguments read in place (megakernel_common.h)
@@ -557,7 +559,9 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
                                            uint32_t* next_sub, long nsub, int pool_min, int refill,
                                            const uint32_t* __restrict__ pixels,
                                            const uint64_t* __restrict__ seeds = nullptr) {
-    using C = Cfg<F | kCfgLdsObj>;  // the object table in LDS (path_f64.h rt_lds_objects)
+    // the object table in LDS (path_f64.h rt_lds_objects); the compact tables read at each use (kCfgTabUse: the
+    // batch windows raised the pool's SGPR spills)
+    using C = Cfg<F | kCfgLdsObj | kCfgTabUse>;
     static_assert(C::mesh && C::compact && !C::bvh, "flat-mesh kernel: compact scenes, octree meshes");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves (path_f64.h: the diagnostic builds' per-wave LDS)");
     static_assert(C::nospec || B == 256, "LdsCold's columns have a stride of 256");
@@ -1013,7 +1017,7 @@ hipError_t launch_render_units_flat_f64(const DevScene& sc, const RenderArgs& a_
 // flat_query reads its mesh through scalar loads and takes wave votes, so the loop over the meshes is uniform
 // (kernel-argument bounds) and a lane only takes part in the query of a mesh whose bit it holds.
 __global__ __launch_bounds__(kBlk) void k_diag_flat(DevScene sc, DiagArgs a, int vis) {
-    using C = Cfg<9>;
+    using C = Cfg<9 | kCfgTabUse>;  // the pool's
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     Ray r;
@@ -1076,7 +1080,7 @@ hipError_t launch_diag_flat(const DevScene& sc, const DiagArgs& a, bool visible,
 // and resolved with flat_query per mesh of defer.meshes; defer.c is added iff no mesh occludes.
 template <int F>
 __global__ __launch_bounds__(kBlk) void k_diag_vertex_flat(DevScene sc, RenderArgs a, DiagVertexArgs v) {
-    using C = Cfg<F | kCfgLdsObj>;
+    using C = Cfg<F | kCfgLdsObj | kCfgTabUse>;
     static_assert(kBlk == 256, "LdsCold's columns have a stride of 256");
     lds_objects_fill(sc);
     __shared__ double s_qo[3 * kBlk], s_qds[4 * kBlk];

@@ -466,7 +466,8 @@ template <int F, int W, int P, bool S, int B = P ? kPoolThreads : 256>
 __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                                uint32_t* next_sub, long nsub, int ksteps, int wmin,
                                                                int refill, int pool_min, int pool_vmin) {
-    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0)>;
+    // (the compact tables read at each use, kCfgTabUse: the batch windows raised the walk pool's SGPR spills)
+    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgTabUse>;
     static_assert(C::mesh && C::compact, "mesh megakernel needs the compact tables");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves, at most 16 (path_f64.h: the diagnostic builds' per-wave LDS)");
     static_assert(!P || (B & (B - 1)) == 0, "the walk queue's ring (one entry per thread) masks its index with B - 1");
@@ -958,7 +959,8 @@ template <int F, bool S, int B, int L>
 __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
                                            uint32_t* next_sub, long nsub, const uint32_t* __restrict__ pixels,
                                            const uint64_t* __restrict__ seeds = nullptr) {
-    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0)>;
+    // (the compact tables read at each use, kCfgTabUse: with the batches C5 measured 0.4% below the parent)
+    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgTabUse>;
     static_assert(C::mesh && C::compact && !C::bvh, "the role-split pool walks octrees");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves, at most 16 (path_f64.h: the diagnostic builds' per-wave LDS)");
 #if RT_KARG_VIEW
@@ -1396,7 +1398,7 @@ RT_DEV bool diag_slots_meshes(const DevScene& sc, const Ray& r, const RayInv& in
 // |y - x| (shadow), then the slot walk of each near mesh in gen order (diag_slots_meshes), merged by consider
 // (closest) or ended by the first blocking hit (shadow). One lane per query, walks run to their end.
 __global__ __launch_bounds__(256) void k_diag_slots(DevScene sc, DiagArgs a, int vis) {
-    using C = Cfg<9>;
+    using C = Cfg<9 | kCfgTabUse>;  // the pools'
     __shared__ int32_t s_anc[kSlotAncLevels * 256];
     LdsAncI32* anc = (LdsAncI32*)s_anc + threadIdx.x;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1434,7 +1436,7 @@ __global__ __launch_bounds__(256) void k_diag_slots(DevScene sc, DiagArgs a, int
 // iff a hit has !(t + 0.001 >= dist), and defer.c is added iff none occludes.
 template <int F, bool kSink>
 __global__ __launch_bounds__(256) void k_diag_vertex_slots(DevScene sc, RenderArgs a, DiagVertexArgs v) {
-    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0)>;
+    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgTabUse>;  // as the pools
     if constexpr (C::ldsobj) lds_objects_fill(sc);
     __shared__ int32_t s_anc[kSlotAncLevels * 256];
     LdsAncI32* anc = (LdsAncI32*)s_anc + threadIdx.x;

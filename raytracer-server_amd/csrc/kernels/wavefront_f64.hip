@@ -317,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void k_wf_shade(DevScene sc, RenderArgs a, 
                                                       const int32_t* __restrict__ hprim, double* sub_buf,
                                                       unsigned long long* counters, int32_t* __restrict__ q2_pos,
                                                       double* __restrict__ q2, uint32_t* q2_cnt, long slots) {
-    using C = Cfg<F>;
+    using C = Cfg<F | kCfgTabUse>;  // the compact tables at each use: the batch windows raised its SGPR spills
     constexpr bool kDefer = C::mesh && C::compact;
     const long n = (long)*cnt_in;
     const long stride = (long)gridDim.x * blockDim.x;
@@ -682,7 +682,7 @@ __global__ __launch_bounds__(kBlock) void k_diag_kids(DevScene sc, DiagArgs a, i
 // mesh with the query's own reciprocals, and defer.c is added iff no mesh occludes.
 template <int F>
 __global__ __launch_bounds__(kBlock) void k_diag_vertex_kids(DevScene sc, RenderArgs a, DiagVertexArgs v) {
-    using C = Cfg<F>;
+    using C = Cfg<F | kCfgTabUse>;  // k_wf_shade's
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= v.n) return;
     PathState ps = diag_vertex_load(v, i);
