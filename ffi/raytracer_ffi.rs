@@ -160,6 +160,12 @@ extern "C" {
         surface_area: *mut f64, vertices: *mut f64, indices: *mut u32, kind: *mut i32, child: *mut i32,
         leaf_off: *mut i32, leaf_cnt: *mut i32, refs: *mut i32,
     ) -> c_int;
+    /// The host-side BVH over the spheres of a scene beyond the small-scene tables (nodes in DFS pre-order,
+    /// leaf runs of scene object indices, the rest list of planes and meshes); any output may be null.
+    pub fn rt_scene_object_bvh(
+        scene: *const RtScene, counts: *mut i64 /* [4] */, boxes: *mut f64, a: *mut i32, count: *mut i32,
+        axis: *mut i32, refs: *mut i32, rest: *mut i32,
+    ) -> c_int;
 
     /// Host buffers: `rgb_out` tile_w * tile_h * 3 bytes; `sub_out` (nullable) tile_w * tile_h * 12
     /// f64 subpixel means before the clamp. `cancel` (nullable): the job's `AtomicBool`

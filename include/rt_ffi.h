@@ -155,6 +155,17 @@ int rt_scene_info(const rt_scene* scene, int64_t info[16]);
 int rt_scene_mesh(const rt_scene* scene, int32_t object, int64_t counts[4] /* nodes, refs, tris, verts */,
                   double bbox[6], double* surface_area, double* vertices, uint32_t* indices,
                   int32_t* kind, int32_t* child, int32_t* leaf_off, int32_t* leaf_cnt, int32_t* refs);
+/* The object BVH (host data, no GPU needed): for a scene that does not fit the kernels' small-scene
+ * tables (more than 16 objects, 4 spheres, 4 axis planes per axis or 8 other objects) and has a sphere, the loader
+ * builds a BVH over the spheres (binned SAH, leaves of at most 4); planes and meshes go on a rest list. This call
+ * reports it. It is not part of the device scene: the kernels test every object of such a scene, as before.
+ * counts: nodes, leaf refs (= spheres), rest-list length, depth of the deepest leaf (root = 0); all 0 without a tree.
+ * Nodes are in DFS pre-order (an inner node's left child is the next node): boxes[n][6] = min xyz, max xyz;
+ * count[n] = 0 for an inner node, whose a[n] is its right child and axis[n] its split axis, else the leaf's size,
+ * its spheres being refs[a[n] .. a[n] + count[n]) (scene object indices, ascending). rest[] = the objects outside the
+ * tree, in scene order. Any output pointer may be NULL. Views answer for their base. */
+int rt_scene_object_bvh(const rt_scene* scene, int64_t counts[4] /* nodes, leaf refs, rest, depth */, double* boxes,
+                        int32_t* a, int32_t* count, int32_t* axis, int32_t* refs, int32_t* rest);
 
 /* Rendering ------------------------------------------------------------------------------- */
 /* Host buffers: rgb_out tile_w*tile_h*3 u8; sub_out (optional) tile_w*tile_h*4*3 f64 subpixel

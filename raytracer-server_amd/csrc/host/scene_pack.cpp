@@ -51,13 +51,123 @@ constexpr int kBins = 16;      // SAH bins per axis
 constexpr int kSahDepth = 16;  // deeper BVH nodes split at the median (depth stays <= kBvhMaxDepth)
 bool bvh_sah_enabled() { return rt::ab_knob("RT_BVH_SAH", 1) != 0; }
 
+struct BvhItem { double lo[3], hi[3], c[3]; int32_t id; };
+// The recursive build shared by the mesh BVHs (items = triangles) and the object BVH (items = spheres): nodes
+// appended to `nodes` (child indices are indices into it); a leaf's run starts at leaf.first() and its items,
+// sorted by id, go to leaf.push(id).
+template <class Leaf>
+struct BvhRec {
+    std::vector<rt::DevBvhNode>& nodes;
+    std::vector<BvhItem>& it;
+    bool sah;
+    Leaf& leaf;
+    int depth_seen = 0;  // the deepest leaf (root = 0)
+    // Binned surface-area heuristic (16 bins per axis over the centroid bounds): the split
+    // minimising area(L) * n(L) + area(R) * n(R); items are partitioned in place (left = lower
+    // centroids along *ax). *mid = b when no split separates the items.
+    static double half_area(const double* lo, const double* hi) {
+        const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+        return dx * dy + dy * dz + dz * dx;
+    }
+    void sah_split(size_t b, size_t e, const double* clo, const double* chi, int* ax_out, size_t* mid) {
+        double best = INFINITY;
+        int best_ax = -1, best_bin = -1;
+        for (int ax = 0; ax < 3; ++ax) {
+            const double ext = chi[ax] - clo[ax];
+            if (!(ext > 0.0)) continue;
+            double lo[kBins][3], hi[kBins][3];
+            size_t cnt[kBins] = {0};
+            for (int q = 0; q < kBins; ++q)
+                for (int k = 0; k < 3; ++k) { lo[q][k] = INFINITY; hi[q][k] = -INFINITY; }
+            for (size_t i = b; i < e; ++i) {
+                int q = (int)((it[i].c[ax] - clo[ax]) / ext * kBins);
+                q = std::min(kBins - 1, std::max(0, q));
+                ++cnt[q];
+                for (int k = 0; k < 3; ++k) {
+                    lo[q][k] = std::min(lo[q][k], it[i].lo[k]);
+                    hi[q][k] = std::max(hi[q][k], it[i].hi[k]);
+                }
+            }
+            double ra[kBins];
+            size_t rc[kBins];
+            double al[3] = {INFINITY, INFINITY, INFINITY}, ah[3] = {-INFINITY, -INFINITY, -INFINITY};
+            size_t ac = 0;
+            for (int q = kBins - 1; q > 0; --q) {  // suffix boxes: bins q..15
+                for (int k = 0; k < 3; ++k) { al[k] = std::min(al[k], lo[q][k]); ah[k] = std::max(ah[k], hi[q][k]); }
+                ac += cnt[q];
+                rc[q] = ac;
+                ra[q] = ac ? half_area(al, ah) : 0.0;
+            }
+            double pl[3] = {INFINITY, INFINITY, INFINITY}, ph[3] = {-INFINITY, -INFINITY, -INFINITY};
+            size_t pc = 0;
+            for (int q = 1; q < kBins; ++q) {  // split between bins q-1 and q
+                for (int k = 0; k < 3; ++k) { pl[k] = std::min(pl[k], lo[q - 1][k]); ph[k] = std::max(ph[k], hi[q - 1][k]); }
+                pc += cnt[q - 1];
+                if (pc == 0 || rc[q] == 0) continue;
+                const double cost = half_area(pl, ph) * (double)pc + ra[q] * (double)rc[q];
+                if (cost < best) { best = cost; best_ax = ax; best_bin = q; }
+            }
+        }
+        *mid = b;
+        if (best_ax < 0) return;
+        const int ax = best_ax;
+        const double ext = chi[ax] - clo[ax];
+        auto left = [&](const BvhItem& x) {
+            int q = (int)((x.c[ax] - clo[ax]) / ext * kBins);
+            return std::min(kBins - 1, std::max(0, q)) < best_bin;
+        };
+        *mid = (size_t)(std::stable_partition(it.begin() + b, it.begin() + e, left) - it.begin());
+        *ax_out = ax;
+    }
+    void build(size_t b, size_t e, int depth) {
+        const size_t node = nodes.size();
+        nodes.push_back(rt::DevBvhNode{});
+        rt::DevBvhNode nd{};
+        double clo[3], chi[3];
+        for (int k = 0; k < 3; ++k) {
+            nd.bmin[k] = clo[k] = INFINITY;
+            nd.bmax[k] = chi[k] = -INFINITY;
+        }
+        for (size_t i = b; i < e; ++i)
+            for (int k = 0; k < 3; ++k) {
+                nd.bmin[k] = std::min(nd.bmin[k], it[i].lo[k]);
+                nd.bmax[k] = std::max(nd.bmax[k], it[i].hi[k]);
+                clo[k] = std::min(clo[k], it[i].c[k]);
+                chi[k] = std::max(chi[k], it[i].c[k]);
+            }
+        if (e - b <= 4 || depth + 1 >= rt::kBvhMaxDepth) {
+            nd.a = leaf.first();
+            nd.count = (int32_t)(e - b);
+            depth_seen = std::max(depth_seen, depth);
+            std::sort(it.begin() + b, it.begin() + e, [](const BvhItem& x, const BvhItem& y) { return x.id < y.id; });
+            for (size_t i = b; i < e; ++i) leaf.push(it[i].id);
+        } else {
+            int ax = 0;
+            size_t mid = 0;
+            if (sah && depth < kSahDepth) sah_split(b, e, clo, chi, &ax, &mid);
+            if (mid <= b || mid >= e) {  // median split (no SAH split found, or deep nodes)
+                ax = 0;
+                for (int k = 1; k < 3; ++k)
+                    if (chi[k] - clo[k] > chi[ax] - clo[ax]) ax = k;
+                mid = (b + e) / 2;
+                std::nth_element(it.begin() + b, it.begin() + mid, it.begin() + e,
+                                 [ax](const BvhItem& x, const BvhItem& y) { return x.c[ax] < y.c[ax] || (x.c[ax] == y.c[ax] && x.id < y.id); });
+            }
+            nd.axis = ax;
+            build(b, mid, depth + 1);
+            nd.a = (int32_t)nodes.size();  // index of the right child (global, for p.bvh)
+            build(mid, e, depth + 1);
+        }
+        nodes[node] = nd;
+    }
+};
+
 void build_bvh(Packed& p, const Mesh& m, int32_t tri_base) {
-    struct Item { double lo[3], hi[3], c[3]; int32_t id; };
     const size_t n = m.num_triangles();
-    std::vector<Item> it(n);
+    std::vector<BvhItem> it(n);
     for (size_t t = 0; t < n; ++t) {
         const D3 v[3] = {m.vertices[m.indices[3 * t]], m.vertices[m.indices[3 * t + 1]], m.vertices[m.indices[3 * t + 2]]};
-        Item& x = it[t];
+        BvhItem& x = it[t];
         x.id = (int32_t)t;
         for (int k = 0; k < 3; ++k) {
             const double a = k == 0 ? v[0].x : k == 1 ? v[0].y : v[0].z;
@@ -68,112 +178,16 @@ void build_bvh(Packed& p, const Mesh& m, int32_t tri_base) {
             x.c[k] = 0.5 * (x.lo[k] + x.hi[k]);
         }
     }
-    struct Rec {
+    struct TriLeaf {  // the leaf's triangles copied to btris, their global indices to btri_id
         Packed& p;
-        std::vector<Item>& it;
         int32_t tri_base;
-        bool sah;
-        // Binned surface-area heuristic (16 bins per axis over the centroid bounds): the split
-        // minimising area(L) * n(L) + area(R) * n(R); items are partitioned in place (left = lower
-        // centroids along *ax). *mid = b when no split separates the items.
-        static double half_area(const double* lo, const double* hi) {
-            const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-            return dx * dy + dy * dz + dz * dx;
+        int32_t first() const { return (int32_t)p.btris.size(); }
+        void push(int32_t id) {
+            p.btris.push_back(p.tris[tri_base + id]);
+            p.btri_id.push_back(tri_base + id);
         }
-        void sah_split(size_t b, size_t e, const double* clo, const double* chi, int* ax_out, size_t* mid) {
-            double best = INFINITY;
-            int best_ax = -1, best_bin = -1;
-            for (int ax = 0; ax < 3; ++ax) {
-                const double ext = chi[ax] - clo[ax];
-                if (!(ext > 0.0)) continue;
-                double lo[kBins][3], hi[kBins][3];
-                size_t cnt[kBins] = {0};
-                for (int q = 0; q < kBins; ++q)
-                    for (int k = 0; k < 3; ++k) { lo[q][k] = INFINITY; hi[q][k] = -INFINITY; }
-                for (size_t i = b; i < e; ++i) {
-                    int q = (int)((it[i].c[ax] - clo[ax]) / ext * kBins);
-                    q = std::min(kBins - 1, std::max(0, q));
-                    ++cnt[q];
-                    for (int k = 0; k < 3; ++k) {
-                        lo[q][k] = std::min(lo[q][k], it[i].lo[k]);
-                        hi[q][k] = std::max(hi[q][k], it[i].hi[k]);
-                    }
-                }
-                double ra[kBins];
-                size_t rc[kBins];
-                double al[3] = {INFINITY, INFINITY, INFINITY}, ah[3] = {-INFINITY, -INFINITY, -INFINITY};
-                size_t ac = 0;
-                for (int q = kBins - 1; q > 0; --q) {  // suffix boxes: bins q..15
-                    for (int k = 0; k < 3; ++k) { al[k] = std::min(al[k], lo[q][k]); ah[k] = std::max(ah[k], hi[q][k]); }
-                    ac += cnt[q];
-                    rc[q] = ac;
-                    ra[q] = ac ? half_area(al, ah) : 0.0;
-                }
-                double pl[3] = {INFINITY, INFINITY, INFINITY}, ph[3] = {-INFINITY, -INFINITY, -INFINITY};
-                size_t pc = 0;
-                for (int q = 1; q < kBins; ++q) {  // split between bins q-1 and q
-                    for (int k = 0; k < 3; ++k) { pl[k] = std::min(pl[k], lo[q - 1][k]); ph[k] = std::max(ph[k], hi[q - 1][k]); }
-                    pc += cnt[q - 1];
-                    if (pc == 0 || rc[q] == 0) continue;
-                    const double cost = half_area(pl, ph) * (double)pc + ra[q] * (double)rc[q];
-                    if (cost < best) { best = cost; best_ax = ax; best_bin = q; }
-                }
-            }
-            *mid = b;
-            if (best_ax < 0) return;
-            const int ax = best_ax;
-            const double ext = chi[ax] - clo[ax];
-            auto left = [&](const Item& x) {
-                int q = (int)((x.c[ax] - clo[ax]) / ext * kBins);
-                return std::min(kBins - 1, std::max(0, q)) < best_bin;
-            };
-            *mid = (size_t)(std::stable_partition(it.begin() + b, it.begin() + e, left) - it.begin());
-            *ax_out = ax;
-        }
-        void build(size_t b, size_t e, int depth) {
-            const size_t node = p.bvh.size();
-            p.bvh.push_back(rt::DevBvhNode{});
-            rt::DevBvhNode nd{};
-            double clo[3], chi[3];
-            for (int k = 0; k < 3; ++k) {
-                nd.bmin[k] = clo[k] = INFINITY;
-                nd.bmax[k] = chi[k] = -INFINITY;
-            }
-            for (size_t i = b; i < e; ++i)
-                for (int k = 0; k < 3; ++k) {
-                    nd.bmin[k] = std::min(nd.bmin[k], it[i].lo[k]);
-                    nd.bmax[k] = std::max(nd.bmax[k], it[i].hi[k]);
-                    clo[k] = std::min(clo[k], it[i].c[k]);
-                    chi[k] = std::max(chi[k], it[i].c[k]);
-                }
-            if (e - b <= 4 || depth + 1 >= rt::kBvhMaxDepth) {
-                nd.a = (int32_t)p.btris.size();
-                nd.count = (int32_t)(e - b);
-                std::sort(it.begin() + b, it.begin() + e, [](const Item& x, const Item& y) { return x.id < y.id; });
-                for (size_t i = b; i < e; ++i) {
-                    p.btris.push_back(p.tris[tri_base + it[i].id]);
-                    p.btri_id.push_back(tri_base + it[i].id);
-                }
-            } else {
-                int ax = 0;
-                size_t mid = 0;
-                if (sah && depth < kSahDepth) sah_split(b, e, clo, chi, &ax, &mid);
-                if (mid <= b || mid >= e) {  // median split (no SAH split found, or deep nodes)
-                    ax = 0;
-                    for (int k = 1; k < 3; ++k)
-                        if (chi[k] - clo[k] > chi[ax] - clo[ax]) ax = k;
-                    mid = (b + e) / 2;
-                    std::nth_element(it.begin() + b, it.begin() + mid, it.begin() + e,
-                                     [ax](const Item& x, const Item& y) { return x.c[ax] < y.c[ax] || (x.c[ax] == y.c[ax] && x.id < y.id); });
-                }
-                nd.axis = ax;
-                build(b, mid, depth + 1);
-                nd.a = (int32_t)p.bvh.size();  // global index of the right child
-                build(mid, e, depth + 1);
-            }
-            p.bvh[node] = nd;
-        }
-    } rec{p, it, tri_base, bvh_sah_enabled()};
+    } leaf{p, tri_base};
+    BvhRec<TriLeaf> rec{p.bvh, it, bvh_sah_enabled(), leaf};
     if (n > 0) rec.build(0, n, 0);
 }
 
@@ -228,6 +242,41 @@ void fill_compact(const Packed& p, rt::CompactTab* ds, int32_t* compact) {
             ds->gen_cull32[g][6] = m.cull32_s;
         }
     }
+}
+
+// The object BVH (scene_pack.hpp ObjectBvh) of a scene that does not fit the compact tables: BvhRec's tree over the
+// spheres (box = centre +- r per axis), the leaf runs of scene object indices, and the rest list (planes and meshes,
+// scene order). Host data only: nothing of it is uploaded. A sphere with a non-finite centre or radius: no tree.
+void build_object_bvh(Packed& p) {
+    if (p.compact) return;
+    ObjectBvh t;
+    std::vector<BvhItem> it;
+    for (size_t i = 0; i < p.objects.size(); ++i) {
+        const rt::DevObject& o = p.objects[i];
+        if (o.geom != rt::GEOM_SPHERE) {
+            t.rest.push_back((int32_t)i);
+            continue;
+        }
+        if (!(std::isfinite(o.pos[0]) && std::isfinite(o.pos[1]) && std::isfinite(o.pos[2]) && std::isfinite(o.r))) return;
+        BvhItem x;
+        x.id = (int32_t)i;
+        for (int k = 0; k < 3; ++k) {
+            x.lo[k] = o.pos[k] - std::fabs(o.r);
+            x.hi[k] = o.pos[k] + std::fabs(o.r);
+            x.c[k] = o.pos[k];
+        }
+        it.push_back(x);
+    }
+    if (it.size() < (size_t)kObvhMinSpheres) return;
+    struct RefLeaf {
+        std::vector<int32_t>& refs;
+        int32_t first() const { return (int32_t)refs.size(); }
+        void push(int32_t id) { refs.push_back(id); }
+    } leaf{t.refs};
+    BvhRec<RefLeaf> rec{t.nodes, it, bvh_sah_enabled(), leaf};
+    rec.build(0, it.size(), 0);
+    t.depth = rec.depth_seen;
+    p.obvh = std::move(t);
 }
 
 // f32 perf-mode tables (scene_layout.h: Obj32 / Bvh32 / Tri32). BVH boxes are rounded outward and
@@ -605,6 +654,7 @@ int pack_scene(const Scene& sc, Packed* out, std::string* err) {
     fill_compact(p, &p.ctab, &p.compact);
     fill_compact32(p.ctab, p.compact, p.ctab32);
     pack_f32(p, &p.obj32, &p.bvh32, &p.btris32, &p.off32);
+    build_object_bvh(p);
     if (sc.light >= 0 && sc.light < (int32_t)p.objects.size()) {
         const rt::DevObject& L = p.objects[sc.light];
         const double PI = 3.14159265358979323846264338327950288;  // path_f64.h PI

@@ -8,6 +8,18 @@
 
 namespace rt::host {
 
+// The BVH over the spheres of a scene that does not fit the compact tables (at least kObvhMinSpheres spheres), as
+// rt_scene_object_bvh reports it. Host data: no kernel walks it and nothing of it is uploaded.
+// nodes are in DFS pre-order as the mesh BVHs' (an inner node's left child is the next node, `a` its right child,
+// `axis` the split axis; indices into `nodes`); a leaf (count > 0) holds refs[a .. a + count), scene object indices,
+// ascending. rest = the scene's planes and meshes, in scene order. depth = the deepest leaf's (root 0).
+constexpr int kObvhMinSpheres = 1;
+struct ObjectBvh {
+    std::vector<rt::DevBvhNode> nodes;
+    std::vector<int32_t> refs, rest;
+    int depth = 0;
+};
+
 // Host image of the device scene, packed once per scene.
 struct Packed {
     std::vector<rt::DevObject> objects;
@@ -32,6 +44,7 @@ struct Packed {
     std::vector<rt::Obj32> obj32;        // f32 perf-mode tables (pack_f32)
     std::vector<rt::Bvh32> bvh32;
     std::vector<rt::Tri32> btris32;
+    ObjectBvh obvh;                      // the BVH over the scene's spheres (host only; empty: no tree)
     float off32 = 0.f;                   // DevScene::off32
     double light_pdf = 0.0;              // DevScene::light_pdf
     bool phong = false, spec = false;    // some object has a Phong / a specular BRDF (RenderArgs::features)

@@ -759,6 +759,31 @@ int rt_scene_mesh(const rt_scene* s, int32_t object, int64_t counts[4], double b
     return RT_OK;
 }
 
+int rt_scene_object_bvh(const rt_scene* s, int64_t counts[4], double* boxes, int32_t* a, int32_t* count, int32_t* axis,
+                        int32_t* refs, int32_t* rest) {
+    if (!s) return fail(RT_E_INVAL, "null argument");
+    const rt::host::ObjectBvh& t = s->packed.obvh;
+    if (counts) {
+        counts[0] = (int64_t)t.nodes.size();
+        counts[1] = (int64_t)t.refs.size();
+        counts[2] = t.nodes.empty() ? 0 : (int64_t)t.rest.size();
+        counts[3] = t.depth;
+    }
+    for (size_t i = 0; i < t.nodes.size(); ++i) {
+        const rt::DevBvhNode& nd = t.nodes[i];
+        if (boxes) {
+            std::memcpy(boxes + 6 * i, nd.bmin, 3 * sizeof(double));
+            std::memcpy(boxes + 6 * i + 3, nd.bmax, 3 * sizeof(double));
+        }
+        if (a) a[i] = nd.a;
+        if (count) count[i] = nd.count;
+        if (axis) axis[i] = nd.axis;
+    }
+    if (refs && !t.refs.empty()) std::memcpy(refs, t.refs.data(), t.refs.size() * sizeof(int32_t));
+    if (rest && !t.nodes.empty() && !t.rest.empty()) std::memcpy(rest, t.rest.data(), t.rest.size() * sizeof(int32_t));
+    return RT_OK;
+}
+
 int rt_render_device(const rt_scene* scene, const rt_render_params* params, void* d_rgb, void* d_sub, void* stream,
                      rt_render_stats* stats) {
     if (!scene || !d_rgb) return fail(RT_E_INVAL, "null argument");

@@ -102,7 +102,7 @@ _EXPORTS = ["rt_scene_load_toml", "rt_scene_create", "rt_scene_destroy", "rt_sce
             "rt_accum_holes_device", "rt_accum_fill", "rt_render_pixels_path", "rt_render_pixels_with",
             "rt_render_pixels_with_device", "rt_render_pixel_passes", "rt_render_pixel_passes_device", "rt_accum_plan",
             "rt_accum_plan_device", "rt_accum_add_passes", "rt_accum_refine", "rt_render_pixel_passes_with",
-            "rt_render_pixel_passes_with_device"]
+            "rt_render_pixel_passes_with_device", "rt_scene_object_bvh"]
 
 
 def _load():
@@ -119,6 +119,9 @@ def _load():
     L.rt_scene_mesh.argtypes = [vp, ctypes.c_int32, P(ctypes.c_int64), P(ctypes.c_double), P(ctypes.c_double),
                                 P(ctypes.c_double), P(ctypes.c_uint32), P(ctypes.c_int32), P(ctypes.c_int32),
                                 P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_int32)]
+    if hasattr(L, "rt_scene_object_bvh"):  # absent from libraries built before it existed (A/B variants)
+        L.rt_scene_object_bvh.argtypes = [vp, P(ctypes.c_int64), P(ctypes.c_double), P(ctypes.c_int32),
+                                          P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_int32)]
     L.rt_render.argtypes = [vp, P(RenderParams), P(ctypes.c_uint8), P(ctypes.c_double), P(ctypes.c_int32),
                             P(RenderStats)]
     L.rt_render_device.argtypes = [vp, P(RenderParams), vp, vp, vp, P(RenderStats)]
@@ -346,6 +349,26 @@ class Scene:
                                  _ptr(cnt, I), _ptr(refs, I)))
         return dict(bbox=bbox, surface_area=sa.value, vertices=verts, indices=idx, kind=kind, child=child,
                     leaf_off=off, leaf_cnt=cnt, refs=refs[:nr])
+
+    def object_bvh(self):
+        """The BVH the loader builds over the spheres of a scene past the small-scene tables (rt_scene_object_bvh;
+        host data, the kernels do not walk it), or None for a scene without one: boxes[n, 6]
+        (min xyz, max xyz), a, count, axis per node in DFS pre-order (count 0: an inner node whose left child is
+        the next node and right child a; else a leaf holding refs[a : a + count]), refs = scene object indices,
+        rest = the objects outside the tree in scene order, depth = the deepest leaf's (root 0)."""
+        counts = np.zeros(4, dtype=np.int64)
+        _check(lib.rt_scene_object_bvh(self._h, _ptr(counts, ctypes.c_int64), None, None, None, None, None, None))
+        nn, nr, nrest, depth = (int(x) for x in counts)
+        if nn == 0:
+            return None
+        boxes = np.zeros((nn, 6))
+        a, cnt, axis = (np.zeros(nn, dtype=np.int32) for _ in range(3))
+        refs = np.zeros(max(1, nr), dtype=np.int32)
+        rest = np.zeros(max(1, nrest), dtype=np.int32)
+        I = ctypes.c_int32
+        _check(lib.rt_scene_object_bvh(self._h, None, _ptr(boxes, ctypes.c_double), _ptr(a, I), _ptr(cnt, I),
+                                       _ptr(axis, I), _ptr(refs, I), _ptr(rest, I)))
+        return dict(boxes=boxes, a=a, count=cnt, axis=axis, refs=refs[:nr], rest=rest[:nrest], depth=depth)
 
     def trace_ray(self, origins, dirs, device=0, mesh_nearest=False):
         o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
