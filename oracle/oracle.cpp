@@ -664,7 +664,8 @@ static V3 reflected(Ctx& c, const Hit& hit, V3 o, uint64_t depth) {
 //   after a diffuse bounce under MIS, on the light, pdf_prev > 0: L += beta (.) Le(x) w
 //   then, not a mirror: L += beta (.) NEE;  Russian roulette;  beta (.)= f cos / (pdf p).
 // variant 0 writes every term with the expressions of `reflected` (the shared helpers above); variant 1 with the
-// device's algebraic forms (integrator_f64.h RT_OPT_NEE / RT_OPT_BETA / RT_OPT_LEF / RT_OPT_KPI), in plain IEEE
+// device's algebraic forms (integrator_f64.h shade_vertex: the NEE term through one reciprocal, the continuation weight
+// as k / p, DevObject::lef; path_f64.h brdf_eval: DevObject::kpi), in plain IEEE
 // arithmetic: with equal libm results it is what a device lane must produce bit for bit.
 enum { K_CAMERA = 0, K_SPEC = 1, K_DIFF = 2 };
 struct VState {

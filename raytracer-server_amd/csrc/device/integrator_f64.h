@@ -17,26 +17,6 @@
 #include "../kernels/kernels.h"
 #include "path_f64.h"
 
-// A/B switches of the shading restructure (1 = on)
-#ifndef RT_OPT_SPEC
-#define RT_OPT_SPEC 1  // mirror vertices share the RR + continuation code of diffuse vertices
-#endif
-#ifndef RT_OPT_VIS
-#define RT_OPT_VIS 1   // the shadow ray reuses norm(y - x) and |y - x| of the NEE term
-#endif
-#ifndef RT_OPT_LEF
-#define RT_OPT_LEF 1   // diffuse NEE: Le * f precomputed per object (DevObject::lef)
-#endif
-#ifndef RT_OPT_RR
-#define RT_OPT_RR 1    // Russian roulette as an integer comparison of the draw (Rng::below53)
-#endif
-#ifndef RT_OPT_NEE
-#define RT_OPT_NEE 1   // the NEE term's scalar factors through one reciprocal (MIS: the weight cancelled)
-#endif
-#ifndef RT_OPT_BETA
-#define RT_OPT_BETA 1  // continuation weight f cos / (pdf p) as k / p (diffuse and mirror vertices)
-#endif
-
 namespace rt {
 namespace f64 {
 
@@ -231,15 +211,10 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
     } else if (C::mis && hr.obj == sc.light && ps.pdf_prev > 0.0) {
         // MIS, BSDF strategy: emitted radiance with the balance-heuristic weight
         double cosl = dot(nrm, -ps.ray.d);
-#if RT_OPT_NEE
         // pdf_prev / (pdf_prev + pdf_l) with pdf_l = pdfA t^2 / cosl: numerator and denominator times cosl
         // (one division; cosl == 0 gives 0 like the reference's pdf_l = inf)
         const double pc = ps.pdf_prev * cosl;
         double wgt = pc / (pc + light_pdf_area(sc) * (hr.t * hr.t));
-#else
-        double pdf_l = light_pdf_area(sc) * (hr.t * hr.t) / cosl;
-        double wgt = ps.pdf_prev / (ps.pdf_prev + pdf_l);
-#endif
         ps.L = ps.L + mult(ps.beta, ld3(obj.emitted) * wgt);
     }
     V3 o = -ps.ray.d;  // the out direction, except after a mirror bounce (which keeps the previous one)
@@ -248,25 +223,6 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
     const double p = ps.depth <= (uint32_t)MAX_BOUNCES ? 1.0 : SURVIVAL_PROBABILITY;
     Rng rng(ps.r0, ps.r1);
     const bool spec = !C::nospec && obj.brdf == BRDF_SPECULAR;
-#if !RT_OPT_SPEC
-    if (spec) {
-        RT_DBG_REGION(7);
-        const bool survive = rng.uniform() < p;  // scene.rs:173
-        ps.r0 = rng.s0;
-        ps.r1 = rng.s1;
-        if (!survive) return false;
-        V3 i;
-        double pdf;
-        brdf_sample<C>(obj, nrm, o, rng, &i, &pdf);
-        V3 f = brdf_eval<C>(obj, nrm, o, i);
-        cold.set_bemit(ps, ps.beta);
-        cold.set_o(ps, o);
-        ps.beta = vdiv<C::g1>(mult(ps.beta, f) * dot(nrm, i), pdf * p);
-        ps.ray = Ray{x, i};
-        ps.kind = K_SPEC;
-        return true;
-    }
-#endif
     const bool use_mis = C::mis && obj.brdf == BRDF_DIFFUSE;
     // next-event estimation (scene.rs:217-229); a mirror vertex has none (scene.rs:170-185)
     if (!spec) {
@@ -278,28 +234,19 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
         RT_DBG_TEND(9, t_ls);
         const V3 diff = y - x;
         const double r_sqr = dot(diff, diff);
-#if RT_OPT_VIS
         // norm(y - x) and |y - x| exactly as mutually_visible computes them (scene.rs:258-262): the
         // shadow ray reuses them
         double dist;                                 // == mag(diff)
         const V3 i = div_sqrt<C::g1>(diff, r_sqr, &dist);  // == norm(diff), one vote (path_f64.h)
-#else
-        const V3 i = norm<C::g1>(diff);
-#endif
         // Le * f: for a diffuse vertex Le_light * (kd / pi), evaluated once per object on the host
         // (mirror vertices have no NEE)
-        V3 lef = (RT_OPT_LEF && (!C::phong || obj.brdf == BRDF_DIFFUSE))
+        V3 lef = (!C::phong || obj.brdf == BRDF_DIFFUSE)
                      ? ld3(obj.lef)
                      : mult(ld3(object_at<C>(sc, sc.light).emitted), brdf_eval<C>(obj, nrm, o, i));
         if (!is_zero(lef)) {  // a zero Le*f makes the term exactly 0: skip the shadow ray
             RT_DBG_REGION(9);
             double vis;
-#if RT_OPT_VIS
             const Ray sr{x, i};
-#else
-            const double dist = mag<C::g1>(diff);
-            const Ray sr{x, vdiv<C::g1>(diff, dist)};
-#endif
             if constexpr (C::mesh && C::compact) {
                 if (defer) {
                     // mutually_visible (scene.rs:258-270) split: analytic objects now, meshes deferred
@@ -333,35 +280,23 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
             }
             V3 c;
             if (!use_mis) {
-#if RT_OPT_NEE
                 // one scalar weight, one reciprocal (magnitude only: the same value up to the last bits)
                 c = lef * (vis * dot(nrm, i) * dot(ny, -i) * rcp_any<C::g1>(r_sqr * pdfA));
-#else
-                c = vdiv<C::g1>(lef * vis * dot(nrm, i) * dot(ny, -i), r_sqr * pdfA);
-#endif
             } else {
                 double cosl = dot(ny, -i);
                 double pdf_l = pdfA * r_sqr / cosl;
                 double pdf_b = dot(nrm, i) * FRAC_1_PI;
                 c = v3(0, 0, 0);
-#if RT_OPT_NEE
                 // (pdf_l / (pdf_l + pdf_b)) / pdf_l == 1 / (pdf_l + pdf_b)
                 if (vis > 0. && cosl > 0. && pdf_b > 0.) c = lef * (dot(nrm, i) * rcp_any<C::g1>(pdf_l + pdf_b));
-#else
-                if (vis > 0. && cosl > 0. && pdf_b > 0.) c = lef * dot(nrm, i) * ((pdf_l / (pdf_l + pdf_b)) / pdf_l);
-#endif
             }
             if (defer && defer->pending) defer->c = mult(ps.beta, c);  // added later iff no mesh occludes
             else ps.L = ps.L + mult(ps.beta, c);
         }
     }
     // Russian roulette (scene.rs:173 / :231) + BSDF continuation (scene.rs:176-184 / :232-240): one
-    // code path for mirror and diffuse vertices
-#if RT_OPT_RR
+    // code path for mirror and diffuse vertices. The roulette is an integer comparison of the draw (Rng::below53)
     if (!rng.below53(ps.depth <= (uint32_t)MAX_BOUNCES ? kP53One : kP53Survive)) return false;  // uniform() < p
-#else
-    if (!(rng.uniform() < p)) return false;
-#endif
     RT_DBG_REGION(10);
     V3 wi;
     double pdf;
@@ -374,7 +309,6 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
         cold.set_bemit(ps, ps.beta);
         cold.set_o(ps, o);
     }
-#if RT_OPT_BETA
     // f cos / (pdf p) with cos and pdf cancelled: diffuse f = kd / pi, pdf = cos / pi (scene.rs:41-43,
     // 56-70); mirror f = ks / cos (wi is exactly flip_across(o, n), so Specular::eval's equal_within
     // holds), pdf = 1 (scene.rs:44-55, 71-74) — both k / p. Same value up to the last bits; cos == 0
@@ -385,10 +319,6 @@ RT_DEV bool shade_vertex(const DevScene& sc, const RenderArgs& a, PathState& ps,
     } else {
         ps.beta = vdiv<C::g1>(mult(ps.beta, brdf_eval<C>(obj, nrm, o, wi)) * cw, pdf * p);
     }
-#else
-    V3 f = brdf_eval<C>(obj, nrm, o, wi);
-    ps.beta = vdiv<C::g1>(mult(ps.beta, f) * dot(nrm, wi), pdf * p);
-#endif
     ps.ray = Ray{x, wi};
     ps.kind = spec ? K_SPEC : K_DIFF;
     ps.pdf_prev = use_mis ? pdf : 0.0;

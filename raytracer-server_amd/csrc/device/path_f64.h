@@ -37,58 +37,37 @@ RT_DEV V3 operator*(double s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
 // (Markstein's theorem; valid without overflow/underflow). Used only when |b| is in
 // [2^-900, 2^900]; otherwise, and for NaN/inf, the plain IEEE division is taken. The sign of a
 // zero quotient is restored from q0 (see qdiv). Bit-identical to a / b for finite a.
-#ifndef RT_OPT_VOTE
-#define RT_OPT_VOTE 2  // A/B: the guards' wave votes as a scalar AND of single-compare ballots (2), as one
-                       // ballot of the conjunction (1: its boolean goes through a VGPR), or __all (0)
-#endif
-#ifndef RT_OPT_NORM1
-#define RT_OPT_NORM1 1  // A/B: a / sqrt(x) behind the square root's vote alone (div_sqrt) (1), or two votes (0)
-#endif
-#ifndef RT_OPT_GUARDI
-#define RT_OPT_GUARDI 1  // A/B: the range guards as unsigned window tests on the high dword (1), f64 compares (0)
-#endif                   // (cornell 1024 spp: votes 2004.6 -> 2093.7, windows 2103.1, profiles/r07_ab_guards.log)
 RT_DEV bool rcp_safe(double b) { return fabs(b) >= 0x1p-900 && fabs(b) <= 0x1p900; }
 // All active lanes satisfy p (a wave vote kept in SGPRs: ballot vs exec, no VGPR round trip).
-RT_DEV bool wave_all(bool p) {
-#if RT_OPT_VOTE
-    return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_read_exec();
-#else
-    return __all(p);
-#endif
-}
+RT_DEV bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_read_exec(); }
 // The guards' votes. A ballot folds into its compare (v_cmp writes the lane mask) only when its argument is
 // one compare; the ballot of a conjunction first materialises the boolean in a VGPR (v_cndmask 0/1, v_cmp_ne:
 // two VALU and a hazard nop per guard). So each range end is a ballot of its own and the masks meet on the
 // scalar side: (ballot(x >= lo) & ballot(x <= hi)) == exec. The same predicate, lane for lane (a NaN fails
-// both forms). RT_OPT_GUARDI makes each range one unsigned window test on the operand's high dword (sign,
-// exponent, top of the mantissa: 32-bit VALU instead of f64 compares, one ballot per operand); the windows
-// hold the same operands, or fewer (rcp: 2^900 itself is left out), so a fast path runs only where it did.
+// both forms). Each range is then one unsigned window test on the operand's high dword (sign, exponent, top
+// of the mantissa: 32-bit VALU instead of f64 compares, one ballot per operand); the windows hold the same
+// operands as the f64 compares, or fewer (rcp: 2^900 itself is left out), so a fast path runs only where it
+// did (cornell 1024 spp: votes 2004.6 -> 2093.7, windows 2103.1, profiles/r07_ab_guards.log).
 RT_DEV uint64_t vote(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 RT_DEV bool vote_all(uint64_t m) { return m == __builtin_amdgcn_read_exec(); }
 RT_DEV uint32_t hi_dword(double x) { return (uint32_t)((uint64_t)__double_as_longlong(x) >> 32); }
-// lanes with |b| in rcp_rn's range [2^-900, 2^900] (RT_OPT_GUARDI: [2^-900, 2^900), a subset: biased
-// exponents 123 .. 1922, one unsigned window on the sign-stripped high dword)
-RT_DEV uint64_t rcp_vote(double b) {
-#if RT_OPT_GUARDI
-    return vote(((hi_dword(b) & 0x7FFFFFFFu) - 0x07B00000u) < 0x70800000u);
-#else
-    return vote(fabs(b) >= 0x1p-900) & vote(fabs(b) <= 0x1p900);
-#endif
-}
-// G1 (Cfg::g1, every guarded helper's template flag): the guards as they were before RT_OPT_VOTE=2 /
-// RT_OPT_NORM1 / RT_OPT_GUARDI, one ballot of the conjunction and two votes per normalise. The fused mesh
-// instances k_megakernel_f64<odd, 3> keep them: they run at their 168-VGPR cap with 150-260 spilled VGPRs, and
-// the new forms, cheaper in instructions, moved their spill counts up in six of eight instances (as
-// walk_step's Hoist flag keeps its hoist out of the instances it costs registers).
-constexpr bool kGuardsNew = RT_OPT_VOTE >= 2;
+// lanes with |b| in [2^-900, 2^900), a subset of rcp_rn's range [2^-900, 2^900]: biased exponents
+// 123 .. 1922, one unsigned window on the sign-stripped high dword
+RT_DEV uint64_t rcp_vote(double b) { return vote(((hi_dword(b) & 0x7FFFFFFFu) - 0x07B00000u) < 0x70800000u); }
+// G1 (Cfg::g1, every guarded helper's template flag): the guards as they were before the single-compare
+// ballots, the window tests and div_sqrt's single vote: one ballot of the conjunction (its boolean goes
+// through a VGPR) and two votes per normalise. The fused mesh instances k_megakernel_f64<odd, 3> keep them:
+// they run at their 168-VGPR cap with 150-260 spilled VGPRs, and the new forms, cheaper in instructions, moved
+// their spill counts up in six of eight instances (as walk_step's Hoist flag keeps its hoist out of the
+// instances it costs registers).
 template <bool G1 = false>
 RT_DEV bool rcp_safe_all(double b) {
-    if constexpr (kGuardsNew && !G1) return vote_all(rcp_vote(b));
+    if constexpr (!G1) return vote_all(rcp_vote(b));
     else return wave_all(rcp_safe(b));
 }
 template <bool G1 = false>
 RT_DEV bool rcp_safe_all(double a, double b, double c) {
-    if constexpr (kGuardsNew && !G1) return vote_all(rcp_vote(a) & rcp_vote(b) & rcp_vote(c));
+    if constexpr (!G1) return vote_all(rcp_vote(a) & rcp_vote(b) & rcp_vote(c));
     else return wave_all(rcp_safe(a) && rcp_safe(b) && rcp_safe(c));
 }
 // RN(1 / b) for rcp_safe(b): the compiler's own IEEE f64 division sequence for 1.0 / b (v_rcp_f64,
@@ -110,20 +89,13 @@ RT_DEV double rcp_any(double b) {
     if (rcp_safe_all<G1>(b)) return rcp_rn(b);
     return 1.0 / b;
 }
-#ifndef RT_OPT_QDIV
-#define RT_OPT_QDIV 1  // A/B: sign of a zero quotient by copysign (1) or by a select on r == 0 (0)
-#endif
 RT_DEV double qdiv(double a, double b, double y) {
     double q0 = a * y;
     double r = fma(-b, q0, a);
-#if RT_OPT_QDIV
     // fma(r, y, q0) is RN(a / b); only a zero quotient (a = +-0) can come out with the wrong sign
     // (+0 + -0 = +0), and q0 = a y already carries the quotient's sign whenever a != 0 (no
     // underflow in range), so the sign bit is taken from q0 (one v_bfi_b32 instead of cmp + 2 selects).
     return __builtin_copysign(fma(r, y, q0), q0);
-#else
-    return r == 0.0 ? q0 : fma(r, y, q0);
-#endif
 }
 template <bool G1 = false>
 RT_DEV V3 vdiv(V3 a, double s) {
@@ -134,9 +106,6 @@ RT_DEV V3 vdiv(V3 a, double s) {
     return v3(a.x / s, a.y / s, a.z / s);
 }
 RT_DEV V3 operator/(V3 a, double s) { return vdiv(a, s); }
-#ifndef RT_OPT_SQRT
-#define RT_OPT_SQRT 1  // A/B: unscaled sqrt sequence behind a wave vote (1) or the library sqrt (0)
-#endif
 // RN(sqrt(x)): for x in [2^-767, inf) the compiler's own f64 sqrt sequence (v_rsq_f64, one
 // Goldschmidt step and two Newton corrections) without its input scaling (an identity in that
 // range: ldexp by 0) and its 0/inf fixup (unreachable there); 11 VALU instead of 17. Other inputs
@@ -152,25 +121,19 @@ RT_DEV double sqrt_fast(double x) {  // x in [2^-767, inf)
     d = fma(-g, g, x);
     return fma(d, h, g);
 }
-// every lane's x is in sqrt_fast's range (RT_OPT_GUARDI: the same set as one unsigned window on the high
-// dword, biased exponents 256 .. 2046 with the sign bit clear)
+// every lane's x is in sqrt_fast's range (x >= 2^-767 && x < inf: the same set as one unsigned window on the
+// high dword, biased exponents 256 .. 2046 with the sign bit clear)
 template <bool G1 = false>
 RT_DEV bool sqrt_fast_all(double x) {
-    if constexpr (kGuardsNew && !G1) {
-#if RT_OPT_GUARDI
+    if constexpr (!G1) {
         return vote_all(vote((hi_dword(x) - 0x10000000u) < 0x6FF00000u));
-#else
-        return vote_all(vote(x >= 0x1p-767) & vote(x < INFINITY));
-#endif
     } else {
         return wave_all(x >= 0x1p-767 && x < INFINITY);
     }
 }
 template <bool G1 = false>
 RT_DEV double sqrt_rn(double x) {
-#if RT_OPT_SQRT
     if (sqrt_fast_all<G1>(x)) return sqrt_fast(x);
-#endif
     return sqrt(x);
 }
 // a / sqrt(x) and *root = sqrt(x), bit for bit `s = sqrt(x); a / s` in IEEE arithmetic, behind the square
@@ -183,7 +146,7 @@ RT_DEV double sqrt_rn(double x) {
 // own squared length (a non-finite a gives a non-finite x); a caller passing an unrelated x must keep it.
 template <bool G1 = false>
 RT_DEV V3 div_sqrt(V3 a, double x, double* root) {
-    if constexpr (RT_OPT_NORM1 && RT_OPT_SQRT && !G1) {
+    if constexpr (!G1) {
         if (sqrt_fast_all(x)) {
             const double s = sqrt_fast(x);
             const double y = rcp_rn(s);
@@ -203,11 +166,9 @@ RT_DEV double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 RT_DEV V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 RT_DEV V3 mult(V3 a, V3 b) { return v3(a.x * b.x, a.y * b.y, a.z * b.z); }
 template <bool G1 = false>
-RT_DEV double mag(V3 a) { return sqrt_rn<G1>(a.x * a.x + a.y * a.y + a.z * a.z); }
-template <bool G1 = false>
 RT_DEV V3 norm(V3 a) {
     double m;
-    return div_sqrt<G1>(a, a.x * a.x + a.y * a.y + a.z * a.z, &m);  // a / mag(a)
+    return div_sqrt<G1>(a, a.x * a.x + a.y * a.y + a.z * a.z, &m);  // a / mag(a), mag = the radicand's sqrt_rn
 }
 RT_DEV bool equal_within(V3 a, V3 b, double e) {
     return fabs(a.x - b.x) < e && fabs(a.y - b.y) < e && fabs(a.z - b.z) < e;
@@ -216,9 +177,6 @@ RT_DEV V3 flip_across(V3 a, V3 axis) { return (2.0 * dot(a, axis)) * axis - a; }
 RT_DEV bool is_zero(V3 a) { return a.x == 0.0 && a.y == 0.0 && a.z == 0.0; }
 RT_DEV double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 RT_DEV V3 clampv(V3 a, double lo, double hi) { return v3(clampd(a.x, lo, hi), clampd(a.y, lo, hi), clampd(a.z, lo, hi)); }
-RT_DEV double det3(V3 v0, V3 v1, V3 v2) {
-    return v0.x * (v1.y * v2.z - v1.z * v2.y) - v1.x * (v0.y * v2.z - v0.z * v2.y) + v2.x * (v0.y * v1.z - v0.z * v1.y);
-}
 RT_DEV double powi(double b, int n) {
     bool neg = n < 0;
     unsigned e = neg ? (unsigned)(-n) : (unsigned)n;
@@ -298,9 +256,6 @@ RT_DEV double div_y(double a, const Ray& r, const RayInv& v) { return qdiv(a, r.
 RT_DEV double div_z(double a, const Ray& r, const RayInv& v) { return qdiv(a, r.d.z, v.rz); }
 
 // ---------------------------------------------------------------- RNG v2
-#ifndef RT_RNG32
-#define RT_RNG32 0
-#endif
 // One xoroshiro128++ stream per camera sample, seeded by Philox4x32-10(key = seed,
 // counter = (pixel, sample, 0, subpixel)); consumed in the reference's draw order along the path.
 struct Rng {
@@ -326,27 +281,6 @@ struct Rng {
         if ((s0 | s1) == 0) s0 = 1;
     }
     static RT_DEV uint64_t rotl(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-#if RT_RNG32
-    // A/B (RNG v3 candidate): xoshiro128++ on the same 128 state bits (x0..x3 = the 32-bit halves of
-    // s0, s1), one 32-bit output per draw, uniform = k * 2^-32
-    static RT_DEV uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
-    RT_DEV uint32_t next32() {
-        uint32_t x0 = (uint32_t)s0, x1 = (uint32_t)(s0 >> 32), x2 = (uint32_t)s1, x3 = (uint32_t)(s1 >> 32);
-        const uint32_t r = rotl32(x0 + x3, 7) + x0;
-        const uint32_t t = x1 << 9;
-        x2 ^= x0;
-        x3 ^= x1;
-        x1 ^= x2;
-        x0 ^= x3;
-        x2 ^= t;
-        x3 = rotl32(x3, 11);
-        s0 = (uint64_t)x0 | ((uint64_t)x1 << 32);
-        s1 = (uint64_t)x2 | ((uint64_t)x3 << 32);
-        return r;
-    }
-    RT_DEV double uniform() { return (double)next32() * 0x1p-32; }
-    RT_DEV bool below53(uint64_t thr) { return ((uint64_t)next32() << 21) < thr; }
-#endif
     RT_DEV uint64_t next() {  // xoroshiro128++
         uint64_t a = s0, b = s1;
         uint64_t r = rotl(a + b, 17) + a;
@@ -355,25 +289,11 @@ struct Rng {
         s1 = rotl(b, 28);
         return r;
     }
-#if !RT_RNG32
-#ifndef RT_OPT_UNIF
-#define RT_OPT_UNIF 0  // A/B: 1 = two 32-bit conversions and one FMA (same bits; measured 0.6% slower on
-                       // cornell_box, profiles/r02_ab.log r02z), 0 = the u64 -> f64 conversion
-#endif
-    // (u64 >> 11) * 2^-53, exactly: the 53-bit value is hi * 2^32 + lo (hi < 2^21); hi * 2^-21 and
-    // lo * 2^-53 are exact and so is their sum, so the FMA returns the exact product
-    RT_DEV double uniform() {
-#if RT_OPT_UNIF
-        const uint64_t v = next() >> 11;
-        return fma((double)(uint32_t)(v >> 32), 0x1p-21, (double)(uint32_t)v * 0x1p-53);
-#else
-        return (double)(next() >> 11) * (1.0 / 9007199254740992.0);
-#endif
-    }
+    // (u64 >> 11) * 2^-53, exactly (the u64 -> f64 conversion of a 53-bit value and a power-of-two scale)
+    RT_DEV double uniform() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }
     // uniform() < p for p = thr * 2^-53 (thr an integer <= 2^53): the draw is v * 2^-53 exactly, so
     // the comparison is v < thr, with no conversion (Russian roulette, scene.rs:173/:231)
     RT_DEV bool below53(uint64_t thr) { return (next() >> 11) < thr; }
-#endif
 };
 // Russian-roulette thresholds as 53-bit integers: p = 1 (depth <= MAX_BOUNCES) and p = 0.9, whose
 // double is M * 2^-53 for an integer M (0.9 lies in [0.5, 1))
@@ -418,31 +338,16 @@ RT_DEV bool plane_t(const DevObject& o, const Ray& ray, const RayInv& inv, doubl
 }
 // Triangle::intersect (geometry.rs:637-670) on the precomputed (a, ab, ac, n); TR = DevTri in any
 // address space (flat_query reads its triangles through a constant-address-space pointer: s_load).
-// The triangle's unit normal: stored (DevTri), or recomputed for a 72-B leaf copy with the host's own
-// operations (rt_api.cpp: Triangle::normal = (c - a).cross(b - a).norm()), so the same bits.
-template <bool G1 = false, class TR>
-RT_DEV V3 tri_normal(const TR& tr) {
-    if constexpr (sizeof(TR) == sizeof(DevTri)) {
-        return ld3(tr.n);
-    } else {
-        const V3 ab = ld3(tr.ab), ac = ld3(tr.ac);
-        const V3 cr = v3(ac.y * ab.z - ac.z * ab.y, ac.z * ab.x - ac.x * ab.z, ac.x * ab.y - ac.y * ab.x);
-        return norm<G1>(cr);
-    }
-}
-#ifndef RT_TRI_MINORS
-#define RT_TRI_MINORS 1  // tri_t's determinants through their shared minors (1), or four det3 calls (0: A/B)
-#endif
 template <bool G1 = false, class TR>
 RT_DEV bool tri_t(const TR& tr, const Ray& ray, double* tout) {
-    V3 n = tri_normal<G1>(tr);
+    V3 n = ld3(tr.n);
     if (fabs(dot(n, ray.d)) < 0.0001) return false;
     V3 ab = ld3(tr.ab), ac = ld3(tr.ac);
     V3 b = ray.o - ld3(tr.a);
     V3 nd = -ray.d;
-#if RT_TRI_MINORS
-    // det3's cofactor expansion of the four determinants with their seven distinct 2x2 minors computed once
-    // (each det3(v0, v1, v2) = v0.x M1 - v1.x M2 + v2.x M3 with the same minors, the same operations)
+    // the cofactor expansion of the reference's four determinants, det3(v0, v1, v2) = v0.x (v1.y v2.z - v1.z v2.y)
+    // - v1.x (v0.y v2.z - v0.z v2.y) + v2.x (v0.y v1.z - v0.z v1.y), with their seven distinct 2x2 minors computed
+    // once (each det3(v0, v1, v2) = v0.x M1 - v1.x M2 + v2.x M3 with the same minors, the same operations)
     const double mA = ab.y * ac.z - ab.z * ac.y, mB = nd.y * ac.z - nd.z * ac.y, mC = nd.y * ab.z - nd.z * ab.y;
     const double mD = b.y * ac.z - b.z * ac.y, mE = b.y * ab.z - b.z * ab.y, mF = nd.y * b.z - nd.z * b.y;
     const double mG = ab.y * b.z - ab.z * b.y;
@@ -450,10 +355,6 @@ RT_DEV bool tri_t(const TR& tr, const Ray& ray, double* tout) {
     double tn = b.x * mA - ab.x * mD + ac.x * mE;    // det3(b, ab, ac)
     double un = nd.x * mD - b.x * mB + ac.x * mF;    // det3(nd, b, ac)
     double vn = nd.x * mG - ab.x * mF + b.x * mC;    // det3(nd, ab, b)
-#else
-    double det = det3(nd, ab, ac);
-    double tn = det3(b, ab, ac), un = det3(nd, b, ac), vn = det3(nd, ab, b);
-#endif
     double t, u, v;
     if (rcp_safe_all<G1>(det)) {  // wave-uniform
         double y = rcp_rn(det);
@@ -567,12 +468,8 @@ RT_DEV uint32_t root_order(const double d2[8]) {
 // the 2^-50 that root_order requires to take its keys as distinct, so this IS root_order's result
 // (a strict order, no tie to break). Returns false otherwise (the caller runs root_order). ~70 VALU
 // instead of the radicands plus the 19-comparator network (~260).
-#ifndef RT_ROOT_GRID
-#define RT_ROOT_GRID 1  // A/B: 0 = always the sorting network
-#endif
 template <class MT>
 RT_DEV bool root_order_grid(const MT& m, const Ray& ray, uint32_t* order) {
-#if RT_ROOT_GRID
     const double o[3] = {ray.o.x, ray.o.y, ray.o.z};
     double dl[3], far[3];
     uint32_t nb[3];
@@ -599,10 +496,6 @@ RT_DEV bool root_order_grid(const MT& m, const Ray& ray, uint32_t* order) {
     *order = N | (N ^ A) << 4 | (N ^ B) << 8 | x3 << 12 | x4 << 16 | (N ^ A ^ C) << 20 | (N ^ B ^ C) << 24 |
              (N ^ A ^ B ^ C) << 28;
     return ok;
-#else
-    (void)m; (void)ray; (void)order;
-    return false;
-#endif
 }
 
 // BoundingBox::intersect(..).is_some() (geometry.rs:977-1036) for all 8 octants of the box
@@ -706,19 +599,8 @@ __shared__ unsigned long long s_dbg_time[16 * 16];
 // Each walk_step does one unit of work (a triangle test, a backtrack, or a child pick that either
 // opens a leaf or descends and masks the new node's children), so a wave can interleave walks of
 // different lengths and refill lanes whose walk ended (persistent traversal kernels).
-#ifndef RT_LTRI_INDEX
-#define RT_LTRI_INDEX 0  // 1: leaf triangle lists as indices into DevScene::tris (3.6 MB for the unicorn);
-                         // 0: per-leaf copies (18 MB). The index adds a dependent load per triangle: 3%
-                         // slower while tri_t loaded triangles one by one, 0.5% once a step's triangles
-                         // are preloaded (profiles/r02_ab.log): the copies stay the default
-#endif
 #ifndef RT_WALK_TIGHT
-#define RT_WALK_TIGHT 1  // A/B: 0 = visit every child whose octant box the ray hits (the reference's walk)
-#endif
-#ifndef RT_WALK_HOIST
-#define RT_WALK_HOIST 1  // the slot walk loads the open leaf's triangles before its node operation (1: unicorn
-                         // +2.4%, no spill at 254 VGPRs with the kernarg views), tests them first with the node
-                         // operation's loads fetched ahead (2: +2.1%), or after it (0) (profiles/r04_ab.log)
+#define RT_WALK_TIGHT 1  // 0 = visit every child whose octant box the ray hits (the reference's walk: walkref.so)
 #endif
 struct OctWalk {
     double mn[3], mx[3];  // box of `cur`
@@ -729,7 +611,8 @@ struct OctWalk {
     uint32_t stk8;        // level 8 (parents exist at depths 0..9; MAX_DEPTH = 10)
     uint32_t order;       // nibble q = octant visited q-th
     int32_t lpos, lend;   // leaf triangle cursor
-    int32_t best;         // nearest triangle so far in the current leaf (ltri index), -1 none
+    int32_t best;         // nearest triangle so far in the current leaf, -1 none (leaf_tris: its ltri index;
+                          // leaf_tris_loaded: its global id)
     double bt;
     // The slot walk's one-leaf buffer (walk_step<true>): the next leaf in visiting order the node walk
     // found while the cursor was still busy (nlf < nle), and whether the node walk is exhausted.
@@ -811,7 +694,7 @@ RT_DEV bool walk_begin(const DevScene& sc, const DevMesh& m, const Ray& ray, con
     uint32_t order;
     const bool grid = root_order_grid(m, ray, &order);
     if (!wave_all(grid)) {
-        // a lane near a tie (or the A/B build without the grid form): the sorting network on the radicands
+        // a lane near a tie: the sorting network on the radicands
         double d2[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -846,47 +729,26 @@ enum : int { WALK_RUN = 0, WALK_HIT = 1, WALK_MISS = 2 };
 #define RT_TRIS_PER_STEP 2
 #endif
 constexpr int kTrisPerStep = RT_TRIS_PER_STEP;
-#ifndef RT_WALK_OPEN_TEST
-#define RT_WALK_OPEN_TEST 0  // 1: a step that opens a leaf also tests its first triangles (measured -10%)
-#endif
 // Up to kTrisPerStep triangles of the open leaf: WALK_RUN (triangles left), WALK_HIT (the leaf is
 // done and has a hit: the first leaf with a hit wins, geometry.rs:1267-1269), or -1 (done, no hit).
-#ifndef RT_TRI_PRELOAD
-#define RT_TRI_PRELOAD 1  // A/B: the step's triangles are loaded whole before any test (1), or by tri_t (0)
-#endif
 template <bool G1 = false>
 RT_DEV int leaf_tris(const DevScene& sc, const Ray& ray, OctWalk& w, double* t, int* prim) {
-#if RT_TRI_PRELOAD
     // All of the step's triangles (96 B each) are loaded up front: tri_t reads a triangle's normal,
     // tests |n . d| and only then its other 72 B, and the next triangle only after that, i.e. four
     // dependent trips to L2 / the Infinity Cache per step. Entries past the leaf's end are clamped
     // to its last one (loaded, never tested).
-    LeafTri tr[kTrisPerStep];
+    DevTri tr[kTrisPerStep];
 #pragma unroll
     for (int j = 0; j < kTrisPerStep; ++j) {
         const int e = max(0, min(w.lpos + j, w.lend - 1));
-#if RT_LTRI_INDEX
-        tr[j] = sc.tris[sc.ltri_id[e]];
-#else
         tr[j] = sc.ltris[e];
-#endif
     }
-#endif
 #pragma unroll
     for (int j = 0; j < kTrisPerStep; ++j) {
         if (w.lpos < w.lend) {
             RT_DBG(4);
             double tt;
-#if RT_TRI_PRELOAD
             if (tri_t<G1>(tr[j], ray, &tt) && (w.best < 0 || tt < w.bt)) {
-#else
-#if RT_LTRI_INDEX
-            const DevTri& trj = sc.tris[sc.ltri_id[w.lpos]];  // leaf list = triangle indices (3.6 MB table)
-#else
-            const LeafTri& trj = sc.ltris[w.lpos];  // leaf list = triangle copies (18 MB for the unicorn)
-#endif
-            if (tri_t<G1>(trj, ray, &tt) && (w.best < 0 || tt < w.bt)) {
-#endif
                 w.bt = tt;
                 w.best = w.lpos;
             }
@@ -902,11 +764,10 @@ RT_DEV int leaf_tris(const DevScene& sc, const Ray& ray, OctWalk& w, double* t, 
     return -1;
 }
 // The tests of leaf_tris on triangles already loaded (the slot walk's hoisted loads, walk_step<true>).
-// tid (RT_LTRI_ID_HOIST): the triangles' global ids, loaded with them; w.best then holds the best
-// triangle's id itself, so a hit needs no dependent ltri_id load at the leaf's end.
+// tid: the triangles' global ids, loaded with them; w.best then holds the best triangle's id itself, so a
+// hit needs no dependent ltri_id load at the leaf's end.
 template <bool G1 = false>
-RT_DEV int leaf_tris_loaded(const DevScene& sc, const Ray& ray, OctWalk& w, const LeafTri* tr, double* t, int* prim,
-                            const int32_t* tid = nullptr) {
+RT_DEV int leaf_tris_loaded(const Ray& ray, OctWalk& w, const DevTri* tr, const int32_t* tid, double* t, int* prim) {
 #pragma unroll
     for (int j = 0; j < kTrisPerStep; ++j) {
         if (w.lpos < w.lend) {
@@ -914,7 +775,7 @@ RT_DEV int leaf_tris_loaded(const DevScene& sc, const Ray& ray, OctWalk& w, cons
             double tt;
             if (tri_t<G1>(tr[j], ray, &tt) && (w.best < 0 || tt < w.bt)) {
                 w.bt = tt;
-                w.best = tid ? tid[j] : w.lpos;
+                w.best = tid[j];
             }
             ++w.lpos;
         }
@@ -922,7 +783,7 @@ RT_DEV int leaf_tris_loaded(const DevScene& sc, const Ray& ray, OctWalk& w, cons
     if (w.lpos < w.lend) return WALK_RUN;
     if (w.best >= 0) {
         *t = w.bt;
-        *prim = tid ? w.best : sc.ltri_id[w.best];
+        *prim = w.best;
         return WALK_HIT;
     }
     return -1;
@@ -934,52 +795,29 @@ RT_DEV int leaf_tris_loaded(const DevScene& sc, const Ray& ray, OctWalk& w, cons
 // and go on with the next child in visiting order.
 // The bound codes decode as base + q * step: rt_api.cpp make_slot keeps the scene's slot tables only when no
 // code was clamped to the 16-bit range, so every decoded bound encloses its subtree's padded triangle bounds.
-// (RT_TIGHT_INF=1: round 4's decode, codes 0 / kTightTop as -inf / +inf, which that guarantee makes dead.)
-#ifndef RT_TIGHT_INF
-#define RT_TIGHT_INF 0
-#endif
-RT_DEV double tight_lo(uint32_t q, double step, double base) {
-    return (RT_TIGHT_INF && q == 0u) ? -INFINITY : fma((double)q, step, base);
-}
-RT_DEV double tight_hi(uint32_t q, double step, double base) {
-    return (RT_TIGHT_INF && q == (uint32_t)kTightTop) ? INFINITY : fma((double)q, step, base);
-}
-// The slab test's final comparison with its 1e-9 relative padding. RT_TIGHT_PAD1: the padding applied once, to
+RT_DEV double tight_bound(uint32_t q, double step, double base) { return fma((double)q, step, base); }
+// The slab test's final comparison with its 1e-9 relative padding: the padding applied once, to
 // the interval ends t0 = max(0, tn_k), t1 = min(inf, tf_k), instead of to every axis' tn_k / tf_k before the max /
 // min: x -> RN(x - RN(1e-9 |x|)) and x -> RN(x + RN(1e-9 |x|)) are non-decreasing in x (between adjacent doubles x
 // moves by an ulp, the padding by 1e-9 of that), so they commute with max and min (and map 0 to 0, inf to inf),
 // and the comparison is the per-axis form's, bit for bit, with 4 VALU instead of 12.
-#ifndef RT_TIGHT_PAD1
-#define RT_TIGHT_PAD1 1
-#endif
-RT_DEV bool tight_padded_le(double t0, double t1) {
-#if RT_TIGHT_PAD1
-    return t0 - 1e-9 * fabs(t0) <= t1 + 1e-9 * fabs(t1);
-#else
-    return t0 <= t1;
-#endif
-}
+RT_DEV bool tight_padded_le(double t0, double t1) { return t0 - 1e-9 * fabs(t0) <= t1 + 1e-9 * fabs(t1); }
 RT_DEV bool kid_tight_hit(const DevMesh& m, const int4& ks, const Ray& ray, const RayInv& inv) {
     const double step = m.tight_step;
     double t0 = 0.0, t1 = INFINITY;
     bool keep = true, force = false;
     // one axis of near_box's slab test (branch-free: no private arrays, no early exits)
     auto axis = [&](uint32_t ql, uint32_t qh, double base, double o, double d, double rc) {
-        const double lo = tight_lo(ql, step, base);
-        const double hi = tight_hi(qh, step, base);
+        const double lo = tight_bound(ql, step, base);
+        const double hi = tight_bound(qh, step, base);
         const bool inr = fabs(d) >= 0x1p-900 && fabs(d) <= 0x1p900;
         const bool tiny = fabs(d) < 0x1p-900;
         force |= !inr && !tiny;                      // NaN / huge: do not cull
         keep &= !tiny || (o >= lo && o <= hi);       // (nearly) parallel slab: origin must lie inside it
         const double ta = (lo - o) * rc, tb = (hi - o) * rc;
         const double tn = fmin(ta, tb), tf = fmax(ta, tb);
-#if RT_TIGHT_PAD1
         t0 = inr ? fmax(t0, tn) : t0;
         t1 = inr ? fmin(t1, tf) : t1;
-#else
-        t0 = inr ? fmax(t0, tn - 1e-9 * fabs(tn)) : t0;
-        t1 = inr ? fmin(t1, tf + 1e-9 * fabs(tf)) : t1;
-#endif
     };
     axis((uint32_t)ks.y & 0xFFFFu, (uint32_t)ks.z >> 16, m.tight_base[0], ray.o.x, ray.d.x, inv.rx);
     axis((uint32_t)ks.y >> 16, (uint32_t)ks.w & 0xFFFFu, m.tight_base[1], ray.o.y, ray.d.y, inv.ry);
@@ -990,24 +828,16 @@ RT_DEV bool kid_tight_hit(const DevMesh& m, const int4& ks, const Ray& ray, cons
 // the wave: walk_node_slots' wave vote), where its `inr` holds on every axis, so `force` and `keep` keep
 // their initial values and every axis updates t0 / t1: the same operations on the same values, hence the
 // same result, without the per-axis range logic.
-#ifndef RT_TIGHT_FAST
-#define RT_TIGHT_FAST 1  // A/B: 0 = always the general form
-#endif
 RT_DEV bool kid_tight_hit_inr(const DevMesh& m, const int4& ks, const Ray& ray, const RayInv& inv) {
     const double step = m.tight_step;
     double t0 = 0.0, t1 = INFINITY;
     auto axis = [&](uint32_t ql, uint32_t qh, double base, double o, double rc) {
-        const double lo = tight_lo(ql, step, base);
-        const double hi = tight_hi(qh, step, base);
+        const double lo = tight_bound(ql, step, base);
+        const double hi = tight_bound(qh, step, base);
         const double ta = (lo - o) * rc, tb = (hi - o) * rc;
         const double tn = fmin(ta, tb), tf = fmax(ta, tb);
-#if RT_TIGHT_PAD1
         t0 = fmax(t0, tn);
         t1 = fmin(t1, tf);
-#else
-        t0 = fmax(t0, tn - 1e-9 * fabs(tn));
-        t1 = fmin(t1, tf + 1e-9 * fabs(tf));
-#endif
     };
     axis((uint32_t)ks.y & 0xFFFFu, (uint32_t)ks.z >> 16, m.tight_base[0], ray.o.x, inv.rx);
     axis((uint32_t)ks.y >> 16, (uint32_t)ks.w & 0xFFFFu, m.tight_base[1], ray.o.y, inv.ry);
@@ -1019,38 +849,18 @@ RT_DEV int4 kid_slot(const DevScene& sc, int32_t cur, uint32_t oi) {
     return *reinterpret_cast<const int4*>(sc.node_slot + 8 * (size_t)cur + oi);
 }
 // The node part of a walk step through the child slots (RT_WALK_TIGHT): as walk_node below, but a
-// pick reads the child's 16-byte slot (entry + subtree triangle bounds) and skips children whose
-// bounds the ray misses (up to two picks per step), and a descent takes the new node's existence
+// pick reads the child's 16-byte slot (entry + subtree triangle bounds; the slots of the next two candidates
+// are loaded together) and skips children whose bounds the ray misses (up to two picks per step: a culled pick
+// is as if the reference found nothing below that child), and a descent takes the new node's existence
 // mask from the entry (no load). `anc` (or null: the pid_up chain): this walk's LDS column of
 // ancestor node ids at depths 0 .. kSlotAncLevels - 1 (stride 256 threads), written at each descent,
 // so a pop reads the node it resumes at from LDS.
-constexpr int kSlotAncLevels = 9;
-#ifndef RT_POP_BOXLOAD
-#define RT_POP_BOXLOAD 1  // A/B: a pop reloads the ancestor's box (1) or rebuilds it from the root (0)
-#endif
-#ifndef RT_SLOT_CULL
-#define RT_SLOT_CULL 1  // A/B: 0 = the slot walk without the subtree-bounds test
-#endif
-#ifndef RT_LTRI_ID_HOIST
-#define RT_LTRI_ID_HOIST 1  // the hoisted triangle loads also load the triangles' ids (leaf_tris_loaded: unicorn +1.5%, r04o), or not (0)
-#endif
-#ifndef RT_SLOT_PAIR
-#define RT_SLOT_PAIR 1  // a pick loads the slots of the next two candidates together (1: unicorn +0.7%, r04j) or one by one (0)
-#endif  // the deepest parents sit at depth 8 (MAX_DEPTH 10, root depth 1)
-// What the next node operation will load, fetched ahead (RT_WALK_HOIST=2: at the start of the step,
-// before its triangle tests): kind 1 = a pick at `cur` (its first candidate's slot), kind 2 = a pop to
-// the ancestor `cur` at level `lv` (its box and its first candidate's slot), 0 = nothing (the root still
-// to be entered, or exhausted). The node state this reads is not touched by the triangle tests, so the
-// node operation after them starts from the same state and uses these values instead of loading.
+constexpr int kSlotAncLevels = 9;  // the deepest parents sit at depth 8 (MAX_DEPTH 10, root depth 1)
 // The deepest ancestor level lv < w.depth whose remaining-children mask pm (stk byte lv; level 8 in stk8) is
-// non-zero, pm = 0 if none: branch-free (RT_POP_CLZ: the highest non-zero byte of the live part of stk by a
-// count of leading zeros) instead of a loop over the levels, whose trip count is the largest over the wave's
-// popping lanes. Parents sit at depths 0..8 of a walk (MAX_DEPTH 10), so w.depth <= 9 and lv <= 8.
-#ifndef RT_POP_CLZ
-#define RT_POP_CLZ 1
-#endif
+// non-zero, pm = 0 if none: branch-free (the highest non-zero byte of the live part of stk by a count of
+// leading zeros) instead of a loop over the levels, whose trip count is the largest over the wave's popping
+// lanes. Parents sit at depths 0..8 of a walk (MAX_DEPTH 10), so w.depth <= 9 and lv <= 8.
 RT_DEV void pop_level(const OctWalk& w, int& lv, uint32_t& pm) {
-#if RT_POP_CLZ
     const int d = w.depth;
     const int nb = min(d, 8);
     const uint64_t live = nb >= 8 ? w.stk : (w.stk & ((1ull << (8 * nb)) - 1ull));
@@ -1060,15 +870,12 @@ RT_DEV void pop_level(const OctWalk& w, int& lv, uint32_t& pm) {
     const bool at8 = d > 8 && w.stk8 != 0u;
     lv = at8 ? 8 : lb;
     pm = at8 ? w.stk8 : pb;
-#else
-    lv = w.depth;
-    pm = 0;
-    while (pm == 0 && lv > 0) {
-        --lv;
-        pm = lv < 8 ? (uint32_t)(w.stk >> (8 * lv)) & 0xFFu : w.stk8;
-    }
-#endif
 }
+// What the next node operation will load, fetched ahead (walk_step's Hoist 2, which no kernel instance uses: at
+// the start of the step, before its triangle tests): kind 1 = a pick at `cur` (its first candidate's slot), kind 2
+// = a pop to the ancestor `cur` at level `lv` (its box and its first candidate's slot), 0 = nothing (the root still
+// to be entered, or exhausted). The node state this reads is not touched by the triangle tests, so the
+// node operation after them starts from the same state and uses these values instead of loading.
 struct SlotPF {
     int4 ks;
     double2 b0, b1, b2;
@@ -1141,29 +948,12 @@ RT_DEV int walk_node_slots(const DevScene& sc, const DevMesh& m, const Ray& ray,
         w.depth = lv;
         w.pm = pm;
         w.path &= (1u << (3 * lv)) - 1u;
-#if RT_POP_BOXLOAD
         // the ancestor's box (DevScene::node_box: the same arithmetic as the descents); only a descent
         // from it reads the box, so the load overlaps the pick's slot load
         const double2* nb = reinterpret_cast<const double2*>(sc.node_box + 6 * (size_t)w.cur);
         const double2 b0 = nb[0], b1 = nb[1], b2 = nb[2];
         w.mn[0] = b0.x; w.mn[1] = b0.y; w.mn[2] = b1.x;
         w.mx[0] = b1.y; w.mx[1] = b2.x; w.mx[2] = b2.y;
-#else
-        // the ancestor's box, rebuilt from the root along the path (the build's own arithmetic)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            w.mn[k] = m.root_box[k];
-            w.mx[k] = m.root_box[3 + k];
-        }
-        for (int l = 0; l < lv; ++l) {
-            const uint32_t oi = (w.path >> (3 * l)) & 7u;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double c = (w.mn[k] + w.mx[k]) / 2.0;
-                if ((oi >> (2 - k)) & 1u) w.mn[k] = c; else w.mx[k] = c;
-            }
-        }
-#endif
     }
     RT_DBG_TEND(13, t_pop);
     RT_DBG_TSTART(t_pick);
@@ -1172,9 +962,8 @@ RT_DEV int walk_node_slots(const DevScene& sc, const DevMesh& m, const Ray& ray,
     int32_t c = kKidEmpty;
     uint32_t oi = 0;
     // wave-uniform: one form of the test per step (each lane's dir_in_range from its walk's start, OctWalk::enter)
-    const bool inr = RT_TIGHT_FAST && wave_all((w.enter & 2u) != 0u);
+    const bool inr = wave_all((w.enter & 2u) != 0u);
     auto tight = [&](const int4& ks) { return inr ? kid_tight_hit_inr(m, ks, ray, inv) : kid_tight_hit(m, ks, ray, inv); };
-#if RT_SLOT_PAIR
     if (!pf) {
         // both candidates' slots loaded at once (one row of node_slot: the same 128-byte line), so a
         // culled first pick does not wait a second memory latency for the second
@@ -1185,7 +974,7 @@ RT_DEV int walk_node_slots(const DevScene& sc, const DevMesh& m, const Ray& ray,
         const int4 ks2 = kid_slot(sc, w.cur, oi2);
         w.pm = pm1;
         oi = oi1;
-        if (!RT_SLOT_CULL || tight(ks1)) {
+        if (tight(ks1)) {
             c = ks1.x;
         } else {
             RT_DBG(6);
@@ -1203,13 +992,12 @@ RT_DEV int walk_node_slots(const DevScene& sc, const DevMesh& m, const Ray& ray,
             c = ks2.x;
         }
     } else
-#endif
-    for (int tries = 0; tries < 2; ++tries) {
+    for (int tries = 0; tries < 2; ++tries) {  // (Hoist 2: the first candidate's slot was fetched ahead)
         const int q = __builtin_ctz(w.pm);
         w.pm &= w.pm - 1u;
         oi = (w.order >> (4 * q)) & 0xF;
         const int4 ks = (pf && pf->kind != 0 && tries == 0) ? pf->ks : kid_slot(sc, w.cur, oi);
-        if (!RT_SLOT_CULL || tight(ks)) {
+        if (tight(ks)) {
             c = ks.x;
             break;
         }
@@ -1338,9 +1126,10 @@ RT_DEV int walk_node(const DevScene& sc, const DevMesh& m, const Ray& ray, const
 // Slots = the slot walk (walk_node_slots, RT_WALK_TIGHT) or the node_kids walk (walk_node); both give
 // the reference's result. (The wavefront's persistent walk kernels use the node_kids walk: the slot
 // walk inlined there trips an AMDGPU backend error, "illegal VGPR to SGPR copy", in ROCm 7.2.)
-// Hoist: RT_WALK_HOIST's modes (below); the Phong / mesh-light instances of the walk pool pass 0, where
-// the hoisted triangles' registers would spill.
-template <bool Slots = (RT_WALK_TIGHT != 0), int AS = 256, int Hoist = RT_WALK_HOIST, class Anc = LdsAncI32, bool G1 = false>
+// Hoist (below): 1 loads the open leaf's triangles before the node operation (unicorn +2.4%, no spill at 254
+// VGPRs with the kernarg views, profiles/r04_ab.log); the Phong / mesh-light instances of the walk pool pass 0,
+// where the hoisted triangles' registers would spill.
+template <bool Slots = (RT_WALK_TIGHT != 0), int AS = 256, int Hoist = 1, class Anc = LdsAncI32, bool G1 = false>
 RT_DEV int walk_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const RayInv& inv, OctWalk& w, double* t,
                      int* prim, Anc* anc = nullptr) {
     RT_DBG(5);
@@ -1350,28 +1139,22 @@ RT_DEV int walk_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const
         // next triangles are tested. Leaves are still tested in visiting order and the first leaf with
         // a hit ends the walk (a leaf the node walk found beyond it is dropped): the same result, in
         // fewer steps, with both parts of a step busy in most lanes.
-        // Hoist 1: the open leaf's triangles (and their ids, RT_LTRI_ID_HOIST) are loaded BEFORE the node
-        // operation: while a leaf is open the node walk only fills the one-leaf buffer (nlf / nle), so the
-        // cursor stays as loaded and the slot load of the pick and the triangle loads are in flight
+        // Hoist 1: the open leaf's triangles (and their ids, leaf_tris_loaded: unicorn +1.5%) are loaded BEFORE
+        // the node operation: while a leaf is open the node walk only fills the one-leaf buffer (nlf / nle), so
+        // the cursor stays as loaded and the slot load of the pick and the triangle loads are in flight
         // together (one memory latency per step instead of two in a row). A leaf the node walk opens into
         // a free cursor is tested from the next step: the same leaves in the same order, the same result.
-        // Hoist 2: triangle tests first, with the next node operation's loads issued before them (the
-        // pick's slot and a pop's box, slot_prefetch). Hoist 0: node operation, then leaf_tris.
+        // Hoist 2 (measured +2.1% against 1's +2.4%; instantiated by no kernel): triangle tests first, with the next
+        // node operation's loads issued before them (the pick's slot and a pop's box, slot_prefetch).
+        // Hoist 0: node operation, then leaf_tris.
         const bool open = w.lpos < w.lend;
-        LeafTri tr[kTrisPerStep];
+        DevTri tr[kTrisPerStep];
         int32_t tid[kTrisPerStep];
         if (Hoist != 0 && open) {
 #pragma unroll
             for (int j = 0; j < kTrisPerStep; ++j) {
-#if RT_LTRI_INDEX
-                // leaf lists as triangle ids only (no ltris uploaded): the triangle from the 3.6 MB table, one
-                // dependent load later (round 6: C4 -2.2%, C5 -3.7% against the copies, profiles/r06aa_ab_oct_ltidx.log)
-                tid[j] = sc.ltri_id[min(w.lpos + j, w.lend - 1)];
-                tr[j] = sc.tris[tid[j]];
-#else
                 tr[j] = sc.ltris[min(w.lpos + j, w.lend - 1)];
-                if (RT_LTRI_ID_HOIST) tid[j] = sc.ltri_id[min(w.lpos + j, w.lend - 1)];
-#endif
+                tid[j] = sc.ltri_id[min(w.lpos + j, w.lend - 1)];
             }
         }
         SlotPF pf;
@@ -1383,7 +1166,7 @@ RT_DEV int walk_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const
         }
         RT_DBG_TSTART(t_lt);
         if (Hoist != 0 ? open : w.lpos < w.lend) {
-            const int st = Hoist != 0 ? leaf_tris_loaded<G1>(sc, ray, w, tr, t, prim, (RT_LTRI_ID_HOIST || RT_LTRI_INDEX) ? tid : nullptr)
+            const int st = Hoist != 0 ? leaf_tris_loaded<G1>(ray, w, tr, tid, t, prim)
                                       : leaf_tris<G1>(sc, ray, w, t, prim);
             if (st == WALK_HIT) {
                 RT_DBG_TEND(12, t_lt);
@@ -1408,14 +1191,7 @@ RT_DEV int walk_step(const DevScene& sc, const DevMesh& m, const Ray& ray, const
     RT_DBG_TEND(12, t_lt);
     if (st >= 0) return st;
     (void)anc;
-    st = walk_node(sc, m, ray, inv, w);
-#if RT_WALK_OPEN_TEST
-    if (st == WALK_RUN && w.lpos < w.lend) {  // a leaf was just opened: its first triangles in this step
-        const int s2 = leaf_tris<G1>(sc, ray, w, t, prim);
-        return s2 >= 0 ? s2 : WALK_RUN;
-    }
-#endif
-    return st;
+    return walk_node(sc, m, ray, inv, w);
 }
 
 // Mesh::intersect's `octree: None` branch (geometry.rs:886-903): the nearest triangle hit, strict <
@@ -1497,7 +1273,7 @@ RT_DEV bool mesh_hit_walk(const DevScene& sc, const DevMesh& m, const Ray& ray, 
     OctWalk w;
     if (!walk_begin<Slots>(sc, m, ray, inv, tmax, w)) return false;
     int st;
-    while ((st = walk_step<Slots, 256, RT_WALK_HOIST, LdsAncI32, G1>(sc, m, ray, inv, w, t, prim)) == WALK_RUN) {
+    while ((st = walk_step<Slots, 256, 1, LdsAncI32, G1>(sc, m, ray, inv, w, t, prim)) == WALK_RUN) {
     }
     return st == WALK_HIT;
 }
@@ -2103,11 +1879,9 @@ RT_DEV bool mesh_occludes(const DevScene& sc, const Ray& r, const RayInv& inv, d
 // ---------------------------------------------------------------- BRDF (scene.rs:30-123)
 template <class C>
 RT_DEV V3 brdf_eval(const DevObject& o, V3 n, V3 out, V3 in) {
-#ifndef RT_OPT_KPI
-#define RT_OPT_KPI 1  // A/B: diffuse f = kd * FRAC_1_PI read from the object (host-evaluated, same bits)
-#endif
-    // (every object of a scene without Phong or mirror objects is diffuse)
-    if ((C::nospec && !C::phong) || o.brdf == BRDF_DIFFUSE) return RT_OPT_KPI ? ld3(o.kpi) : ld3(o.k) * FRAC_1_PI;
+    // (every object of a scene without Phong or mirror objects is diffuse); diffuse f = kd * FRAC_1_PI read from
+    // the object (host-evaluated, same bits)
+    if ((C::nospec && !C::phong) || o.brdf == BRDF_DIFFUSE) return ld3(o.kpi);
     if (!C::phong || o.brdf == BRDF_SPECULAR) {
         if (equal_within(in, flip_across(out, n), 0.001)) return vdiv<C::g1>(ld3(o.k), dot(n, in));
         return v3(0, 0, 0);

@@ -116,26 +116,13 @@ RT_LAYOUT_FN int32_t slot_parent(int32_t node, uint32_t exist) { return node | (
 RT_LAYOUT_FN int32_t slot_node(int32_t e) { return e & (kSlotMaxNode - 1); }
 RT_LAYOUT_FN uint32_t slot_exist(int32_t e) { return (uint32_t)e >> 23; }
 // node_up[node] = {parent node (-1 at the root), octant slot in the parent}
-// leaf_span[leaf] = {first entry of the leaf in ltri_id (ltris in RT_LTRI_INDEX=0 builds), count}
+// leaf_span[leaf] = {first entry of the leaf in ltris / ltri_id, count}
 
 // Triangle, precomputed exactly as Triangle::intersect derives it per call (geometry.rs:637-653):
 // a, ab = b - a, ac = c - a, n = ((c - a) x (b - a)).norm(). 12 doubles = 96 B.
 struct DevTri {
     double a[3], ab[3], ac[3], n[3];
 };
-// The octree leaves' triangle copies (DevScene::ltris): DevTri, or in RT_LTRI72 builds 72 B without the
-// normal, which the walk's test recomputes with the host's operations (tri_normal, path_f64.h).
-#ifndef RT_LTRI72
-#define RT_LTRI72 0
-#endif
-struct DevTri72 {
-    double a[3], ab[3], ac[3];
-};
-#if RT_LTRI72
-typedef DevTri72 LeafTri;
-#else
-typedef DevTri LeafTri;
-#endif
 
 // Compact per-type object tables, passed in the kernel arguments so the trace loops are unrolled
 // and their operands live in scalar registers (no per-object loads or type branches). Objects keep
@@ -206,7 +193,7 @@ struct DevScene {
     const int32_t* node_kids;   // [node][8], see kid_leaf (leaf triangle ranges inline)
     const int2* node_up;        // [node] {parent, slot}
     const int2* leaf_span;      // [leaf] {first ltri, count}
-    const LeafTri* ltris;       // RT_LTRI_INDEX=0 builds only: leaf triangle lists as copies, in leaf order
+    const DevTri* ltris;        // leaf triangle lists as copies, in leaf order
                                 // (the reference's leaves hold (index, Triangle) copies, geometry.rs:1131-1137)
     const int32_t* ltri_id;     // [ltri] leaf triangle lists as global triangle indices into `tris`, in leaf
                                 // order (the walk's triangles and the hit's `prim`)

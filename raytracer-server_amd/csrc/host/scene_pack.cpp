@@ -7,10 +7,6 @@
 
 #include "../ab_knobs.h"
 
-#ifndef RT_LTRI_INDEX
-#define RT_LTRI_INDEX 0  // the device's switch (path_f64.h, which no host unit can include); variant builds set it for
-#endif                   // both. 1: leaf triangle lists as indices, no per-leaf copies packed
-
 namespace rt::host {
 namespace {
 
@@ -449,16 +445,7 @@ int pack_scene(const Scene& sc, Packed* out, std::string* err) {
             p.leaves.push_back(int2{(int32_t)p.ltri_id.size(), oc.leaf_cnt[i]});
             for (int32_t r = 0; r < oc.leaf_cnt[i]; ++r) {
                 const int32_t t = oc.refs[oc.leaf_off[i] + r];
-#if !RT_LTRI_INDEX
-                const rt::DevTri& lt = p.tris[dm.tri_base + t];
-#if RT_LTRI72
-                rt::LeafTri l72{};
-                for (int k = 0; k < 3; ++k) { l72.a[k] = lt.a[k]; l72.ab[k] = lt.ab[k]; l72.ac[k] = lt.ac[k]; }
-                p.ltris.push_back(l72);
-#else
-                p.ltris.push_back(lt);
-#endif
-#endif
+                p.ltris.push_back(p.tris[dm.tri_base + t]);
                 p.ltri_id.push_back(dm.tri_base + t);
             }
         }

@@ -27,7 +27,7 @@ struct Packed {
     std::vector<int32_t> kids;   // [node][8]
     std::vector<int2> up;        // [node]
     std::vector<int2> leaves;    // [leaf] {first ltri, count}
-    std::vector<rt::LeafTri> ltris;
+    std::vector<rt::DevTri> ltris;
     std::vector<int32_t> ltri_id;
     std::vector<rt::DevTri> tris;
     std::vector<double> cum_area;

@@ -34,10 +34,7 @@ __device__ __forceinline__ long wave_ticket(uint32_t* counter, bool want) {
 // and SGPR hazard nops in a VALU-bound loop; 54 SGPR + 4 VGPR spills in k_megakernel_f64<8,4>). The
 // megakernels take DevScene and RenderArgs as their first two arguments: by the AMDGPU kernarg layout
 // at offset 0 and at sizeof(DevScene) rounded up to RenderArgs' alignment (248: the code objects'
-// .args metadata). RT_KARG_VIEW=0 builds keep the by-value arguments (A/B).
-#ifndef RT_KARG_VIEW
-#define RT_KARG_VIEW 1
-#endif
+// .args metadata).
 typedef const __attribute__((address_space(4))) char KargByte;
 constexpr size_t kKargArgsOffset = (sizeof(DevScene) + alignof(RenderArgs) - 1) / alignof(RenderArgs) * alignof(RenderArgs);
 static_assert(kKargArgsOffset == 248, "DevScene / RenderArgs kernarg layout changed: check the .args metadata");
@@ -324,21 +321,12 @@ static inline void plan_tail(RenderArgs& a, long nsub, long lanes, double* tail_
 // subpixel's sub_buf entry; every later chunk stores each sample's radiance for k_tail_sum_f64, which
 // continues the same sequential sum from chunk 0's partial (the same bits as one lane summing all).
 __device__ __forceinline__ bool tail_in_place(const RenderArgs& a, int s) { return (s >> a.chunk_lg) == 0; }
-#ifndef RT_TAIL_PROBE
-#define RT_TAIL_PROBE 0  // diagnostic builds only: 1 = every lane stores to one slot of its own (wrong frames; the
-                         // per-sample stores' footprint without their scatter)
-#endif
 // tail_buf layout: subpixel-major, [j][s - c0][3] (j = id - n_whole): a chunk's lane writes one contiguous run.
 // (Groups of 64 subpixels, sample-major with a row per component, made k_tail_sum's loads contiguous, 1.0 -> 0.46 ms
 // at N = 8, but scattered these stores: the frame ran 0.1-0.3% slower, profiles/r06an_ab_tail_layout.log.)
 __device__ __forceinline__ void tail_store(const RenderArgs& a, int id, int s, const f64::V3& L) {
-#if RT_TAIL_PROBE == 1
-    (void)id; (void)s;
-    double* o = a.tail_buf + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 3;
-#else
     const int c0 = 1 << a.chunk_lg;
     double* o = a.tail_buf + ((size_t)(id - a.n_whole) * (size_t)(a.n_samples - c0) + (size_t)(s - c0)) * 3;
-#endif
     o[0] = L.x;
     o[1] = L.y;
     o[2] = L.z;

@@ -37,20 +37,10 @@ typedef __attribute__((address_space(3))) double LdsDouble;
 typedef __attribute__((address_space(3))) int32_t LdsInt;
 typedef __attribute__((address_space(3))) uint64_t LdsU64;
 
-#ifndef RT_OPT_LDSOBJ
-#define RT_OPT_LDSOBJ 1  // A/B: the object table in LDS (per-lane object reads as ds_read)
-#endif
-#ifndef RT_MK_BEGIN_AT_END
-#define RT_MK_BEGIN_AT_END 1  // a lane whose sample ended starts its next buffered sample in the same divergent block
-#endif                        // (0: at the top of the next iteration, a block of its own; cornell 1024 spp 2000.6 ->
-                              // 2002.9, C2 MIS 1891.0 -> 1896.6, same frames: profiles/r06be_ab_begin_at_end.log)
 #ifndef RT_MK_MIN_RUN
 #define RT_MK_MIN_RUN 32  // samples per ticket at least, while the frame holds more than one run per lane (plan_units;
 #endif                     // 1080p at 64 spp: 16 -> 1567.5, 24 / 32 -> 1804-1808, 64 -> 1744.9, 128 -> 1664.9 Msamples/s,
                            // profiles/r06br_ab_min_run_long.log, r06bs_ab_min_run_short.log)
-#ifndef RT_OPT_COLD
-#define RT_OPT_COLD 1  // A/B: mirror-bounce state (o, pre-bounce throughput) in LDS (LdsCold) or registers
-#endif
 
 // Diagnostic builds (RT_DEBUG_TIMERS): each wave of k_megakernel_f64 records, on the constant 100 MHz clock
 // (s_memrealtime), when it started, when fewer than half of its lanes last held work (-1: never), and when it
@@ -82,8 +72,7 @@ __device__ unsigned long long g_dbg_wave[kDbgWaveRec * kDbgWaves];
 // instance needs no register beyond the list's; the seed is an 8-byte load beside the camera sample's arithmetic.
 // (kFrame / kList / kPasses, kPassShift and kPassPixMask: integrator_f64.h, shared with the pool bodies)
 template <int F, int L>
-__device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
-                                           uint32_t* next_sub, long nsub, int refill,
+__device__ __forceinline__ void fused_body(double* __restrict__ sub_buf, uint32_t* next_sub, long nsub, int refill,
                                            const uint32_t* __restrict__ pixels,
                                            const uint64_t* __restrict__ seeds = nullptr) {
     // Compact scenes (<= kMaxCompactObjects objects): the object table is copied into LDS, so the
@@ -92,15 +81,10 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
     // register cap, and the new guards raised their spill counts)
     // and, with the Phong + MIS mesh-free instance F = 14 (its pixel-list and batched-pass kernels), read the
     // compact tables at each use (kCfgTabUse: the batch windows raised their spill counts)
-    using C = Cfg<F | ((RT_OPT_LDSOBJ && (F & 8)) ? kCfgLdsObj : 0) | ((F & 1) ? kCfgGuards1 | kCfgTabUse : 0) |
+    using C = Cfg<F | ((F & 8) ? kCfgLdsObj : 0) | ((F & 1) ? kCfgGuards1 | kCfgTabUse : 0) |
                   (F == 14 ? kCfgTabUse : 0)>;
-#if RT_KARG_VIEW
-    const DevScene& sc = karg_scene();  // the arguments read in place (megakernel_common.h)
+    const DevScene& sc = karg_scene();  // the kernel's first two arguments, read in place (megakernel_common.h)
     const RenderArgs& a = karg_render_args();
-#else
-    const DevScene& sc = sc_g;
-    const RenderArgs& a = a_g;
-#endif
     if constexpr (C::ldsobj) lds_objects_fill(sc);
     // Rarely touched per-lane state lives in LDS (one column per thread; VGPRs are the limit at 4
     // waves/SIMD): the subpixel accumulator (once per sample) and the camera-sample buffer — a ring
@@ -109,12 +93,8 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
     // ended each iteration otherwise runs every iteration at that lane utilisation).
     __shared__ double s_acc[3 * 256], s_nbd[kCamDepth * 3 * 256];
     __shared__ uint64_t s_nbr[kCamDepth * 2 * 256];
-#if RT_OPT_COLD
     __shared__ double s_cold[6 * 256];  // integrator_f64.h LdsCold: o and the pre-bounce throughput of mirror paths
     const LdsCold cold{(LdsDouble*)s_cold + threadIdx.x};
-#else
-    const RegCold cold{};
-#endif
     LdsDouble* acc_l = (LdsDouble*)s_acc + threadIdx.x;  // component k at [k * 256]
     LdsDouble* nbd = (LdsDouble*)s_nbd + threadIdx.x;     // slot q, component k at [(q * 3 + k) * 256]
     LdsU64* nbr = (LdsU64*)s_nbr + threadIdx.x;           // slot q, word k at [(q * 2 + k) * 256]
@@ -155,16 +135,9 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
         RT_DBG_REGION(0);
         RT_DBG_TSTART(t_it);
         bool done = false;
-        // camera: a lane starting a path takes its next buffered sample, or joins the camera pass
+        // (timer 1 of the diagnostic build: the block in which a lane took its next buffered sample at the top of
+        // the iteration; it now does so where the last sample ended, below, and the timer reads its own overhead)
         RT_DBG_TSTART(t_fr);
-        if (!RT_MK_BEGIN_AT_END && active && fresh && nbuf > 0) {
-            RT_DBG_REGION(2);
-            const int q = hb * 3 * 256, r = hb * 2 * 256;
-            begin_path(sc, CameraSample{v3(nbd[q], nbd[q + 256], nbd[q + 512]), nbr[r], nbr[r + 256]}, ps);
-            fresh = false;
-            hb = hb + 1 == kCamDepth ? 0 : hb + 1;
-            --nbuf;
-        }
         RT_DBG_TEND(1, t_fr);
         RT_DBG_TSTART(t_rf);
         // camera pass: lanes that start a path now without a buffered sample (sample s), plus lanes
@@ -249,9 +222,9 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
                     done = !unit_has_next(a, id, s);
                     ++s;
                 }
-#if RT_MK_BEGIN_AT_END
                 // the next sample of the same unit from the camera buffer, here rather than in a block of its own
-                // at the top of the next iteration (same lanes; the camera pass below sees the same ring state)
+                // at the top of the next iteration (same lanes; the camera pass below sees the same ring state:
+                // cornell 1024 spp 2000.6 -> 2002.9, C2 MIS 1891.0 -> 1896.6, profiles/r06be_ab_begin_at_end.log)
                 if (!done && nbuf > 0) {
                     const int q = hb * 3 * 256, r = hb * 2 * 256;
                     begin_path(sc, CameraSample{v3(nbd[q], nbd[q + 256], nbd[q + 512]), nbr[r], nbr[r + 256]}, ps);
@@ -259,7 +232,6 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
                     hb = hb + 1 == kCamDepth ? 0 : hb + 1;
                     --nbuf;
                 }
-#endif
             }
             RT_DBG_TEND(6, t_se);
         }
@@ -327,14 +299,14 @@ __device__ __forceinline__ void fused_body(const DevScene& sc_g, const RenderArg
 template <int F, int W>
 __global__ __launch_bounds__(256, W) void k_megakernel_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                           uint32_t* next_sub, long nsub, int refill) {
-    fused_body<F, kFrame>(sc_g, a_g, sub_buf, next_sub, nsub, refill, nullptr);
+    fused_body<F, kFrame>(sub_buf, next_sub, nsub, refill, nullptr);
 }
 // The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
 template <int F, int W>
 __global__ __launch_bounds__(256, W) void k_render_list_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                            uint32_t* next_sub, long nsub, int refill,
                                                            const uint32_t* __restrict__ pixels) {
-    fused_body<F, kList>(sc_g, a_g, sub_buf, next_sub, nsub, refill, pixels);
+    fused_body<F, kList>(sub_buf, next_sub, nsub, refill, pixels);
 }
 // The batched-passes instance: nsub = 4 n_units units, units[u] = pixel | pass << 28 (pass < 16),
 // seeds[16] on the device, sub_buf the compact [n_units][4][3] buffer. Scheduling is the list instance's.
@@ -343,7 +315,7 @@ __global__ __launch_bounds__(256, W) void k_render_passes_f64(DevScene sc_g, Ren
                                                              uint32_t* next_sub, long nsub, int refill,
                                                              const uint32_t* __restrict__ units,
                                                              const uint64_t* __restrict__ seeds) {
-    fused_body<F, kPasses>(sc_g, a_g, sub_buf, next_sub, nsub, refill, units, seeds);
+    fused_body<F, kPasses>(sub_buf, next_sub, nsub, refill, units, seeds);
 }
 
 // Split tail: subpixel n_whole + j's mean, continuing the sequential sum chunk 0 left in sub_buf (its lane
@@ -530,11 +502,11 @@ hipError_t launch_diag_vertex_fused(const DevScene& sc, const RenderArgs& a, con
     } else if (guards == 2) {
         if (bvh) RT_DV_SWITCH(25 | kCfgGuards1 | kCfgTabUse, false) else RT_DV_SWITCH(9 | kCfgGuards1 | kCfgTabUse, false)
     } else if (!mesh) {  // fused_body's C: F | kCfgLdsObj for a compact scene, | kCfgGuards1 with meshes
-        RT_DV_SWITCH(8 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0), RT_OPT_COLD != 0)
+        RT_DV_SWITCH(8 | kCfgLdsObj, true)
     } else if (bvh) {
-        RT_DV_SWITCH(25 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgGuards1 | kCfgTabUse, RT_OPT_COLD != 0)
+        RT_DV_SWITCH(25 | kCfgLdsObj | kCfgGuards1 | kCfgTabUse, true)
     } else {
-        RT_DV_SWITCH(9 | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgGuards1 | kCfgTabUse, RT_OPT_COLD != 0)
+        RT_DV_SWITCH(9 | kCfgLdsObj | kCfgGuards1 | kCfgTabUse, true)
     }
 #undef RT_DV_SWITCH
 #undef RT_DV_CASE

@@ -153,9 +153,6 @@ typedef const __attribute__((address_space(4))) DevTri CTri;
 // lists are in triangle order, so the earlier hit is the lower index: the walk's strict <). Same
 // bits as flat_query_leaves, without its per-leaf best-hit updates (8 leaves x 4 VALU per triangle).
 // The ray reciprocals are taken only for lanes whose ray hits a triangle (the leaf boxes' test).
-#ifndef RT_FLAT_GRID_ORDER
-#define RT_FLAT_GRID_ORDER 1  // the winning leaf by root_order_grid's order (1) or first_visited's argmin (0: A/B)
-#endif
 RT_DEV bool flat_query(const DevScene& sc, int mi, const Ray& ray, double* t_out, int* prim_out) {
     CMesh* M = (CMesh*)(uintptr_t)(sc.meshes + mi);
     const int n = M->n_tris, base = M->tri_base;
@@ -194,7 +191,6 @@ RT_DEV bool flat_query(const DevScene& sc, int mi, const Ray& ray, double* t_out
             for (int k = 0; k < 6; ++k) rb[k] = M->root_box[k];
             cand &= octant_mask(rb, rb + 3, ray, make_inv(ray.d));  // the children's box_hit, bit i = octant i
             if (cand) {
-#if RT_FLAT_GRID_ORDER
                 // the whole visiting order from the octant centres' grid (path_f64.h root_order_grid: root_order's
                 // result whenever no two radicands are near a tie), its first candidate; else first_visited
                 uint32_t order;
@@ -207,9 +203,6 @@ RT_DEV bool flat_query(const DevScene& sc, int mi, const Ray& ray, double* t_out
                 } else {
                     win = first_visited(*M, ray, cand);
                 }
-#else
-                win = first_visited(*M, ray, cand);
-#endif
             }
         }
     }
@@ -241,15 +234,11 @@ RT_DEV void enqueue(int32_t* cnt, int32_t* queue, bool want) {
 // results t / prim to rt / rp [mesh][lane]) followed by its shadow queries (ray + |y - x| in qs;
 // result occluded to ro [mesh][lane], mutually_visible: the walk's hit t with t + 0.001 < |y - x|):
 // flat_query is the same for both, so one chunk serves both kinds.
-#ifndef RT_FLAT_MERGE_KINDS
-#define RT_FLAT_MERGE_KINDS 1
-#endif
 RT_DEV void process_queries(const DevScene& sc, const int32_t* cnt_c, const int32_t* queue_c, const int32_t* cnt_s,
                             const int32_t* queue_s, const LdsD* qc, const LdsD* qs, double* rt, int32_t* rp,
                             int32_t* ro, int first) {
     const int wv = threadIdx.x >> 6, ln = __lane_id();
     int ci = first;
-#if RT_FLAT_MERGE_KINDS
     for (int m = 0; m < sc.n_meshes; ++m) {
         const int nc = cnt_c[m], c = nc + cnt_s[m];
         for (int k = 0; k * 64 < c; ++k, ++ci) {
@@ -275,36 +264,6 @@ RT_DEV void process_queries(const DevScene& sc, const int32_t* cnt_c, const int3
             }
         }
     }
-#else
-    for (int kind = 0; kind < 2; ++kind) {
-        const int32_t* cnt = kind ? cnt_s : cnt_c;
-        const int32_t* queue = kind ? queue_s : queue_c;
-        const LdsD* q = kind ? qs : qc;
-        for (int m = 0; m < sc.n_meshes; ++m) {
-            const int c = cnt[m];
-            for (int k = 0; k * 64 < c; ++k, ++ci) {
-                if ((ci & 3) != wv) continue;
-                const int e = k * 64 + ln;
-                RT_DBG_WAVE(13, lane_id_is0());
-                RT_DBG_WAVE(12, e < c);
-                if (e < c) {
-                    const int who = queue[m * kBlk + e];
-                    const Ray r{v3(q[who], q[kBlk + who], q[2 * kBlk + who]),
-                                v3(q[3 * kBlk + who], q[4 * kBlk + who], q[5 * kBlk + who])};
-                    double t = 0.0;
-                    int prim = -1;
-                    const bool hit = flat_query(sc, m, r, &t, &prim);
-                    if (kind == 0) {
-                        rt[m * kBlk + who] = t;
-                        rp[m * kBlk + who] = hit ? prim : -1;
-                    } else {
-                        ro[m * kBlk + who] = hit && !(t + 0.001 >= q[6 * kBlk + who]) ? 1 : 0;
-                    }
-                }
-            }
-        }
-    }
-#endif
 }
 
 }  // namespace
@@ -316,13 +275,8 @@ __global__ __launch_bounds__(kBlk, W) void k_megakernel_flat_f64(DevScene sc_g, 
     // batch windows raised the pool's SGPR spills)
     using C = Cfg<F | kCfgLdsObj | kCfgTabUse>;
     static_assert(C::mesh && C::compact && !C::bvh, "flat-mesh kernel: compact scenes, octree meshes");
-#if RT_KARG_VIEW
     const DevScene& sc = karg_scene();  // the arguments read in place (megakernel_common.h)
     const RenderArgs& a = karg_render_args();
-#else
-    const DevScene& sc = sc_g;
-    const RenderArgs& a = a_g;
-#endif
     lds_objects_fill(sc);
     // per lane (one column per thread): subpixel accumulator; the closest-hit query ray (o, d), the
     // shadow query ray (o, d, |y - x|); results per (mesh, lane); queues per (kind, parity, mesh):
@@ -539,14 +493,8 @@ __global__ __launch_bounds__(kBlk, W) void k_megakernel_flat_f64(DevScene sc_g, 
                              // 768 (3 waves/SIMD, profiles/r05w_ab_fp.log), which the running sums in sub_buf and
                              // the 16-bit rings made fit the LDS; or 256 (three blocks per CU, A/B)
 #endif
-#ifndef RT_FPOOL_PRIO
-#define RT_FPOOL_PRIO 1  // the query chunks (stage 1) at raised issue priority (s_setprio 1: cubes +1.3%, r04ao), or not (0)
-#endif
 #ifndef RT_FPOOL_READY
 #define RT_FPOOL_READY 16  // a wave with at least this many ready paths waits for chunks of pool_min queries
-#endif
-#ifndef RT_FPOOL_SINK
-#define RT_FPOOL_SINK 1  // A/B: shade_vertex writes the shadow query's ray into the LDS columns (LdsQuerySink)
 #endif
 
 // The kernel's body, shared by its frame instances (L = kFrame: k_megakernel_fpool_f64, units are the tile's
@@ -555,8 +503,8 @@ __global__ __launch_bounds__(kBlk, W) void k_megakernel_flat_f64(DevScene sc_g, 
 // unit 4 u + j is subpixel j of the frame pixel in the word pixels[u], drawn from seeds[the word's pass]; DESIGN.md
 // §18). Everything but unit_subpixel and unit_seed, at the two camera samples, works on the compact unit id.
 template <int F, int B, int L>
-__device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
-                                           uint32_t* next_sub, long nsub, int pool_min, int refill,
+__device__ __forceinline__ void fpool_body(double* __restrict__ sub_buf, uint32_t* next_sub, long nsub, int pool_min,
+                                           int refill,
                                            const uint32_t* __restrict__ pixels,
                                            const uint64_t* __restrict__ seeds = nullptr) {
     // the object table in LDS (path_f64.h rt_lds_objects); the compact tables read at each use (kCfgTabUse: the
@@ -567,13 +515,8 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
     static_assert(C::nospec || B == 256, "LdsCold's columns have a stride of 256");
     // per mesh: at most B closest-hit + B shadow queries queued at once (a power of two)
     constexpr int kRing = B <= 256 ? 512 : B <= 512 ? 1024 : 2048;
-#if RT_KARG_VIEW
     const DevScene& sc = karg_scene();  // the arguments read in place (megakernel_common.h)
     const RenderArgs& a = karg_render_args();
-#else
-    const DevScene& sc = sc_g;
-    const RenderArgs& a = a_g;
-#endif
     lds_objects_fill(sc);
     // per lane (one column per thread): the closest-hit query ray (o, d), the
     // shadow query ray (o, d, |y - x|); results per (mesh, lane); queries outstanding per lane
@@ -642,9 +585,7 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
         RT_DBG_WAVE(8, lane_id_is0());
         RT_DBG_TSTART(t_q);
         // ---------------- (1) queued mesh queries, a chunk per mesh
-#if RT_FPOOL_PRIO
-        __builtin_amdgcn_s_setprio(RT_FPOOL_PRIO);  // A/B: the query chunks at raised issue priority (this level)
-#endif
+        __builtin_amdgcn_s_setprio(1);  // the query chunks at raised issue priority (cubes +1.3%)
         {
             const bool rdy = active && __hip_atomic_load(&s_pend[tid], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0;
             // full chunks while this wave has paths to go on with; anything queued once most of its
@@ -678,19 +619,13 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
                 }
             }
         }
-#if RT_FPOOL_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         RT_DBG_TEND(1, t_q);
         RT_DBG_TSTART(t_v);
         // ---------------- (2) paths whose queries are all answered
         const bool ready = active && __hip_atomic_load(&s_pend[tid], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0;
         RT_DBG_WAVE(9, ready);
         bool finish = false, shadow_q = false;
-#if !RT_FPOOL_SINK
-        Ray sr{v3(0, 0, 0), v3(0, 0, 1)};
-        double dist = 0.0;
-#endif
         uint32_t near_s = 0;
         if (ready) {
             if (spend) {  // the last vertex's NEE term, unless a mesh blocks its shadow ray (mutually_visible)
@@ -717,13 +652,9 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
                 ShadowDefer df;
                 df.pending = false;
                 df.c = v3(0.0, 0.0, 0.0);
-#if RT_FPOOL_SINK
                 // the shadow query's ray goes straight into this lane's query columns (its s_pend read 0)
                 const LdsQuerySink qsink{(LdsD*)s_qo + tid, (LdsD*)s_qds + tid, B};
                 const bool cont = shade_vertex<C, Cold, LdsQuerySink>(sc, a, ps, h, &df, cold, qsink);
-#else
-                const bool cont = shade_vertex<C, Cold>(sc, a, ps, h, &df, cold);
-#endif
                 traced = false;
                 // pc is read only after a shadow query set it (spend): taking df.c unconditionally makes the old
                 // value dead through shade_vertex, the kernel's register peak (the 1024-thread instance: 29 -> 21
@@ -732,10 +663,6 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
                 pc = df.c;
                 if (df.pending) {  // the analytic objects let the shadow ray through; a mesh may block it
                     shadow_q = true;
-#if !RT_FPOOL_SINK
-                    dist = df.dist;
-                    sr = Ray{df.o, df.d};
-#endif
                     near_s = df.meshes;
                 }
                 if (!cont) {
@@ -751,11 +678,6 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
         if (shadow_q) {
             want_s = near_s;  // shade_vertex's mesh_near_mask of the segment (non-zero: df.pending)
             if (want_s) {
-#if !RT_FPOOL_SINK
-                s_qo[tid] = sr.o.x; s_qo[B + tid] = sr.o.y; s_qo[2 * B + tid] = sr.o.z;
-                s_qds[tid] = sr.d.x; s_qds[B + tid] = sr.d.y; s_qds[2 * B + tid] = sr.d.z;
-                s_qds[3 * B + tid] = dist;
-#endif
                 spend = true;
                 smask = want_s;
             } else {  // no mesh near the shadow segment: unblocked now
@@ -870,7 +792,7 @@ __device__ __forceinline__ void fpool_body(const DevScene& sc_g, const RenderArg
 template <int F, int W, int B = kBlk>
 __global__ __launch_bounds__(B, W) void k_megakernel_fpool_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                                  uint32_t* next_sub, long nsub, int pool_min, int refill) {
-    fpool_body<F, B, kFrame>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, nullptr);
+    fpool_body<F, B, kFrame>(sub_buf, next_sub, nsub, pool_min, refill, nullptr);
 }
 // The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
 template <int F, int W, int B = kBlk>
@@ -878,7 +800,7 @@ __global__ __launch_bounds__(B, W) void k_megakernel_fpool_list_f64(DevScene sc_
                                                                       double* __restrict__ sub_buf, uint32_t* next_sub,
                                                                       long nsub, int pool_min, int refill,
                                                                       const uint32_t* __restrict__ pixels) {
-    fpool_body<F, B, kList>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, pixels);
+    fpool_body<F, B, kList>(sub_buf, next_sub, nsub, pool_min, refill, pixels);
 }
 // The batched-passes instance: nsub = 4 n_units units, units[u] = pixel | pass << 28 (pass < 16),
 // seeds[16] on the device, sub_buf the compact [n_units][4][3] buffer. Scheduling is the list instance's.
@@ -888,7 +810,7 @@ __global__ __launch_bounds__(B, W) void k_megakernel_fpool_passes_f64(DevScene s
                                                                         long nsub, int pool_min, int refill,
                                                                         const uint32_t* __restrict__ units,
                                                                         const uint64_t* __restrict__ seeds) {
-    fpool_body<F, B, kPasses>(sc_g, a_g, sub_buf, next_sub, nsub, pool_min, refill, units, seeds);
+    fpool_body<F, B, kPasses>(sub_buf, next_sub, nsub, pool_min, refill, units, seeds);
 }
 
 // One launch of the query pool, with its split tail planned: a frame (L = kFrame), a pixel list (kList: nsub =
@@ -1075,7 +997,7 @@ hipError_t launch_diag_flat(const DevScene& sc, const DiagArgs& a, bool visible,
 // rt_diag_vertex, the query pool's deferred-shadow form: the split trace of k_diag_flat (analytic part, near mask,
 // flat_query per near mesh, merged in gen order), then shade_vertex as fpool_body calls it: C = Cfg<F | kCfgLdsObj>
 // with the pool's nospec bit, Cold = RegCold for a nospec instance and LdsCold on a [6][256] column otherwise, and
-// (RT_FPOOL_SINK) LdsQuerySink writing a pending shadow ray into this lane's query columns, origin [3][256] and
+// LdsQuerySink writing a pending shadow ray into this lane's query columns, origin [3][256] and
 // direction + distance [4][256]. The shadow ray is read back from those columns, as stage 1 of the pool reads it,
 // and resolved with flat_query per mesh of defer.meshes; defer.c is added iff no mesh occludes.
 template <int F>
@@ -1124,26 +1046,17 @@ __global__ __launch_bounds__(kBlk) void k_diag_vertex_flat(DevScene sc, RenderAr
     df.pending = false;
     df.meshes = 0u;
     df.c = v3(0.0, 0.0, 0.0);
-#if RT_FPOOL_SINK
     const LdsQuerySink qsink{(LdsD*)s_qo + tid, (LdsD*)s_qds + tid, kBlk};
     const bool cont = shade_vertex<C, Cold, LdsQuerySink>(sc, a, ps, h, &df, cold, qsink);
-#else
-    const bool cont = shade_vertex<C, Cold>(sc, a, ps, h, &df, cold);
-#endif
     const uint32_t smask = df.pending ? df.meshes : 0u;
     bool occluded = false;
 #pragma unroll
     for (int m = 0; m < kFlatMeshes; ++m) {
         if (m < sc.n_meshes && ((smask >> m) & 1u)) {
-#if RT_FPOOL_SINK
             const LdsD* qo = (const LdsD*)s_qo;
             const LdsD* q = (const LdsD*)s_qds;
             const Ray sr{v3(qo[tid], qo[kBlk + tid], qo[2 * kBlk + tid]), v3(q[tid], q[kBlk + tid], q[2 * kBlk + tid])};
             const double dist = q[3 * kBlk + tid];
-#else
-            const Ray sr{df.o, df.d};
-            const double dist = df.dist;
-#endif
             double t = 0.0;
             int prim = -1;
             const bool hit = flat_query(sc, m, sr, &t, &prim);

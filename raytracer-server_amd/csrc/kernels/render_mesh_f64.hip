@@ -18,9 +18,6 @@ using namespace f64;
 typedef __attribute__((address_space(3))) double LdsDouble;
 typedef __attribute__((address_space(3))) int32_t LdsInt;
 typedef __attribute__((address_space(3))) uint64_t LdsU64;
-#ifndef RT_OPT_LDSOBJ
-#define RT_OPT_LDSOBJ 1  // A/B: the object table in LDS (per-lane object reads as ds_read)
-#endif
 
 // Begins the octree walk of the next candidate mesh after gen slot g (Scene::trace_ray's /
 // mutually_visible's loop over the mesh objects); false when no mesh is left. S: the slot walk
@@ -256,7 +253,7 @@ RT_DEV bool walk_round(const DevScene& sc, const Park& pk, const bool wk, const 
                 } else {
                     double t;
                     int prim;
-                    const int st = walk_step<S, 256, C::phong ? 0 : RT_WALK_HOIST>(sc, sc.meshes[r.mi], r.wr, r.wi, r.w, &t, &prim);
+                    const int st = walk_step<S, 256, C::phong ? 0 : 1>(sc, sc.meshes[r.mi], r.wr, r.wi, r.w, &t, &prim);
                     if (st != WALK_RUN) {
                         if (closest) {
                             if (st == WALK_HIT) {
@@ -301,15 +298,8 @@ struct WalkPool {
     uint8_t* status;    // LDS [block] per owner column: 0 closest query, 1 shadow query, 2 done
 };
 enum : uint8_t { POOL_CLOSEST = 0, POOL_SHADOW = 1, POOL_DONE = 2 };
-#ifndef RT_POOL_PRIO
-#define RT_POOL_PRIO 1  // the walk round at raised issue priority (s_setprio 1: its dependent loads issue ahead of the
-                        // other wave's shading; unicorn +2.3%, r04an), 0 = none, 2 = the vertex phase raised (-2.1%)
-#endif
 #ifndef RT_POOL_REFILL
 #define RT_POOL_REFILL 32
-#endif
-#ifndef RT_POOL_CAMBUF
-#define RT_POOL_CAMBUF 1  // A/B: the walk pool keeps a camera-sample buffer (refill pass) as k_megakernel_f64
 #endif
 constexpr int kPoolRefill = RT_POOL_REFILL;  // refill only when at least this many lanes of the round are idle
 
@@ -318,11 +308,7 @@ constexpr int kPoolRefill = RT_POOL_REFILL;  // refill only when at least this m
 // registers), depth / pm / stk8 packed in one word. Doubles: ray o, d; box mn, mx; walk best t;
 // query t (closest hit so far / shadow distance). Ints: cur, depth | pm << 8 | stk8 << 16, path,
 // stk (2 words), order, lpos, lend, best, hit object, hit prim, gen slot, mesh, occluded.
-#ifndef RT_PARK_INV
-#define RT_PARK_INV 0  // A/B: the park keeps 1/d (1) or park2_load recomputes it (0; its 6 KB of LDS hold the
-                       // pool's camera-sample buffer instead, RT_POOL_CAMBUF)
-#endif
-constexpr int kPark2D = RT_PARK_INV ? 17 : 14, kPark2I = 17;
+constexpr int kPark2D = 14, kPark2I = 17;
 enum : int { P2_T = 13, P2_HOBJ = 9, P2_HPRIM = 10, P2_OCC = 13, P2_NEAR = 16 };
 RT_DEV void park2_store(const Park2& p, const WalkRegs& r) {
     p.D(0) = r.wr.o.x; p.D(1) = r.wr.o.y; p.D(2) = r.wr.o.z;
@@ -330,9 +316,6 @@ RT_DEV void park2_store(const Park2& p, const WalkRegs& r) {
     for (int k = 0; k < 3; ++k) { p.D(6 + k) = r.w.mn[k]; p.D(9 + k) = r.w.mx[k]; }
     p.D(12) = r.w.bt;
     p.D(13) = r.wt;
-#if RT_PARK_INV
-    p.D(14) = r.wi.rx; p.D(15) = r.wi.ry; p.D(16) = r.wi.rz;
-#endif
     p.I(0) = r.w.cur;
     p.I(1) = (int32_t)((uint32_t)r.w.depth | (r.w.pm << 8) | (r.w.stk8 << 16) | (r.w.ndone << 24) | (r.w.enter << 25));
     p.I(2) = (int32_t)r.w.path;
@@ -344,11 +327,7 @@ RT_DEV void park2_store(const Park2& p, const WalkRegs& r) {
 RT_DEV void park2_load(const Park2& p, WalkRegs& r) {
     r.wr.o = v3(p.D(0), p.D(1), p.D(2));
     r.wr.d = v3(p.D(3), p.D(4), p.D(5));
-#if RT_PARK_INV
-    r.wi.rx = p.D(14); r.wi.ry = p.D(15); r.wi.rz = p.D(16);
-#else
     r.wi = make_inv(r.wr.d);
-#endif
     for (int k = 0; k < 3; ++k) { r.w.mn[k] = p.D(6 + k); r.w.mx[k] = p.D(9 + k); }
     r.w.bt = p.D(12);
     r.wt = p.D(13);
@@ -366,11 +345,7 @@ RT_DEV void park2_load(const Park2& p, WalkRegs& r) {
 RT_DEV void park2_query(const Park2& p, const Ray& r, const RayInv& wi, double wt, int32_t hobj, int32_t hprim,
                         uint32_t near) {
     p.I(P2_NEAR) = (int32_t)near;
-#if RT_PARK_INV
-    p.D(14) = wi.rx; p.D(15) = wi.ry; p.D(16) = wi.rz;
-#else
-    (void)wi;
-#endif
+    (void)wi;  // (not parked: park2_load recomputes it)
     p.D(0) = r.o.x; p.D(1) = r.o.y; p.D(2) = r.o.z;
     p.D(3) = r.d.x; p.D(4) = r.d.y; p.D(5) = r.d.z;
     p.D(13) = wt;
@@ -415,7 +390,7 @@ RT_DEV bool pool_round(const DevScene& sc, const WalkPool& wp, LdsDouble* park_d
             if (!fin && r.w.cur >= 0) {
                 double t;
                 int prim;
-                const int st = walk_step<S, kPoolThreads, C::phong ? 0 : RT_WALK_HOIST>(sc, sc.meshes[r.mi], r.wr, r.wi, r.w, &t, &prim,
+                const int st = walk_step<S, kPoolThreads, C::phong ? 0 : 1>(sc, sc.meshes[r.mi], r.wr, r.wi, r.w, &t, &prim,
                                             S ? (LdsAncI32*)park_i + kPark2I * kPoolThreads + q : nullptr);
                 if (st != WALK_RUN) {
                     if (closest) {
@@ -467,18 +442,13 @@ __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, Ren
                                                                uint32_t* next_sub, long nsub, int ksteps, int wmin,
                                                                int refill, int pool_min, int pool_vmin) {
     // (the compact tables read at each use, kCfgTabUse: the batch windows raised the walk pool's SGPR spills)
-    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgTabUse>;
+    using C = Cfg<F | kCfgLdsObj | kCfgTabUse>;
     static_assert(C::mesh && C::compact, "mesh megakernel needs the compact tables");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves, at most 16 (path_f64.h: the diagnostic builds' per-wave LDS)");
     static_assert(!P || (B & (B - 1)) == 0, "the walk queue's ring (one entry per thread) masks its index with B - 1");
     // object table in LDS, as in k_megakernel_f64; the arguments read in place (megakernel_common.h)
-#if RT_KARG_VIEW
     const DevScene& sc = karg_scene();
     const RenderArgs& a = karg_render_args();
-#else
-    const DevScene& sc = sc_g;
-    const RenderArgs& a = a_g;
-#endif
     if constexpr (C::ldsobj) lds_objects_fill(sc);
     __shared__ double s_park_d[(P ? kPark2D : kParkD) * B];
     // pool: + the slot walk's ancestor ids (walk_node_slots)
@@ -497,14 +467,12 @@ __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, Ren
         __syncthreads();
     }
     // subpixel accumulator and camera-sample buffer in LDS, as in k_megakernel_f64 (pool mode: the
-    // buffer's 10 KB fit beside the park at 2 blocks per CU without the parked 1/d, RT_PARK_INV = 0)
-    constexpr bool kCamBuf = !P || RT_POOL_CAMBUF;
-    __shared__ double s_acc[3 * B], s_nbd[kCamBuf ? 3 * B : 1];
-    __shared__ uint64_t s_nbr[kCamBuf ? 2 * B : 1];
+    // buffer's 10 KB fit beside the park at 2 blocks per CU without a parked 1/d)
+    __shared__ double s_acc[3 * B], s_nbd[3 * B];
+    __shared__ uint64_t s_nbr[2 * B];
     LdsDouble* acc_l = (LdsDouble*)s_acc + threadIdx.x;
-    LdsDouble* nbd = (LdsDouble*)s_nbd + (kCamBuf ? threadIdx.x : 0);
-    LdsU64* nbr = (LdsU64*)s_nbr + (kCamBuf ? threadIdx.x : 0);
-    if constexpr (!kCamBuf) refill = 0;
+    LdsDouble* nbd = (LdsDouble*)s_nbd + threadIdx.x;
+    LdsU64* nbr = (LdsU64*)s_nbr + threadIdx.x;
     V3 pc = v3(0, 0, 0);  // pool: the pending shadow query's NEE term (the park has no room for it)
     uint32_t nverts = 0;
     // tickets: whole subpixels, then the split tail's chunks (unit_of), as in k_megakernel_f64
@@ -531,13 +499,11 @@ __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, Ren
         if constexpr (P) {
             // take queued queries (at least pool_min of them while this wave has paths to shade)
             const int ready = __popcll(__ballot(active && !walking));
-#if RT_POOL_PRIO == 1
-            __builtin_amdgcn_s_setprio(1);  // A/B: the walk round at raised issue priority
-#endif
+            // the walk round at raised issue priority: its dependent loads issue ahead of the other wave's shading
+            // (unicorn +2.3%)
+            __builtin_amdgcn_s_setprio(1);
             took = pool_round<C, S>(sc, wp, (LdsDouble*)s_park_d, (LdsInt*)s_park_i, ready ? pool_min : 1, ksteps);
-#if RT_POOL_PRIO == 1
             __builtin_amdgcn_s_setprio(0);
-#endif
             if (!took && !ready) {
                 __builtin_amdgcn_s_sleep(2);  // every path of this wave waits on walks other waves hold
             }
@@ -552,9 +518,6 @@ __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, Ren
         const bool was_walking = walking;
         // pool: after a walk round, shade only once pool_vmin paths are ready (denser vertex phases)
         const bool vphase = !P || !took || __popcll(__ballot(active && !walking)) >= pool_vmin;
-#if RT_POOL_PRIO == 2
-        __builtin_amdgcn_s_setprio(1);  // A/B: the vertex phase at raised issue priority (lowered at the iteration's end)
-#endif
         RT_DBG_WAVE(9, vphase && active && !walking);
         if constexpr (P) {
           // Pool kernel: per iteration a ready path first shades the hit it holds (the closest walk's
@@ -637,7 +600,7 @@ __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, Ren
             // the next ray, unless a shadow query is pending or the unit is done (a new ticket first)
             if (!walking && !done) {
                 if (fresh) {
-                    if (kCamBuf && nvalid) begin_path(sc, CameraSample{v3(nbd[0], nbd[B], nbd[2 * B]), nbr[0], nbr[B]}, ps);
+                    if (nvalid) begin_path(sc, CameraSample{v3(nbd[0], nbd[B], nbd[2 * B]), nbr[0], nbr[B]}, ps);
                     else begin_sample(sc, a, subpixel_of(a, id), s, ps);
                     nvalid = false;
                     fresh = false;
@@ -794,9 +757,6 @@ __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, Ren
         }
         RT_DBG_TEND(4, t_bk);
         RT_DBG_TEND(0, t_it);
-#if RT_POOL_PRIO == 2
-        __builtin_amdgcn_s_setprio(0);
-#endif
     }
     flush_count(a.counters, nverts);
     RT_DBG_TFLUSH();
@@ -825,9 +785,6 @@ __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, Ren
 #ifndef RT_ROLES_REFILL
 #define RT_ROLES_REFILL 16  // a walker wave refills once at least this many of its lanes are idle
 #endif
-#ifndef RT_ROLES_PRIO
-#define RT_ROLES_PRIO 1  // walker waves at raised issue priority, this s_setprio level (their dependent loads issue first)
-#endif
 #ifndef RT_ROLES_BLOCK
 #define RT_ROLES_BLOCK 768  // threads of a block (one per CU: the path store takes the LDS): 3 waves/SIMD (168 VGPRs);
                             // 512 threads (2 waves/SIMD) with 512 paths measured 17% slower (profiles/r05l_ab_b768.log)
@@ -846,10 +803,6 @@ __global__ __launch_bounds__(B, W) void k_megakernel_mesh_f64(DevScene sc_g, Ren
 #ifndef RT_ROLES_PATHS_MIS
 #define RT_ROLES_PATHS_MIS (752 - RT_ROLES_DBG_LDS)
 #endif
-#ifndef RT_ANC16
-#define RT_ANC16 1  // the walkers' ancestor columns hold 16-bit pids (scenes with more parents pop through pid_up)
-#endif
-using AncT = std::conditional_t<RT_ANC16 != 0, uint16_t, int32_t>;
 // Block shape per instance: the Phong instances (the Phong BRDF's shading code: 32 spilled VGPRs at the
 // 168 of 3 waves/SIMD) keep 512-thread blocks, 2 waves/SIMD, half of them walkers.
 template <class C>
@@ -956,20 +909,15 @@ RT_DEV void role_query_closest(const RP& P, int p, const HitRec& h, uint32_t nea
 // unit 4 u + j is subpixel j of the frame pixel in the word pixels[u], drawn from seeds[the word's pass]; DESIGN.md
 // §18). Everything but unit_subpixel and unit_seed, at the one camera sample, works on the compact unit id.
 template <int F, bool S, int B, int L>
-__device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArgs& a_g, double* __restrict__ sub_buf,
-                                           uint32_t* next_sub, long nsub, const uint32_t* __restrict__ pixels,
+__device__ __forceinline__ void roles_body(double* __restrict__ sub_buf, uint32_t* next_sub, long nsub,
+                                           const uint32_t* __restrict__ pixels,
                                            const uint64_t* __restrict__ seeds = nullptr) {
     // (the compact tables read at each use, kCfgTabUse: with the batches C5 measured 0.4% below the parent)
-    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgTabUse>;
+    using C = Cfg<F | kCfgLdsObj | kCfgTabUse>;
     static_assert(C::mesh && C::compact && !C::bvh, "the role-split pool walks octrees");
     static_assert(B % 64 == 0 && B <= 1024, "whole waves, at most 16 (path_f64.h: the diagnostic builds' per-wave LDS)");
-#if RT_KARG_VIEW
     const DevScene& sc = karg_scene();
     const RenderArgs& a = karg_render_args();
-#else
-    const DevScene& sc = sc_g;
-    const RenderArgs& a = a_g;
-#endif
     if constexpr (C::ldsobj) lds_objects_fill(sc);
     using RL = RoleLayout<C>;
     constexpr int NP = RL::paths, kRing = RL::ring;
@@ -980,8 +928,8 @@ __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArg
     __shared__ uint32_t s_qhead[2][2], s_qtail[2][2];
     using RS = RoleShape<C>;
     static_assert(RS::block == B, "the launch's block shape");
-    // walker lanes' ancestor columns: 16-bit pids (RT_ANC16) when the scene's pids fit, else the pid_up chain
-    __shared__ AncT s_anc[S ? kSlotAncLevels * RS::walk_threads : 1];
+    // walker lanes' ancestor columns: 16-bit pids when the scene's pids fit, else the pops go through the pid_up chain
+    __shared__ uint16_t s_anc[S ? kSlotAncLevels * RS::walk_threads : 1];
     __shared__ uint32_t s_live;  // path slots still holding work (the block ends at 0)
     const RolePaths<NP> P{(LdsDouble*)s_pd, (LdsU64*)s_pu, (LdsInt*)s_pi};
     const LdsQueue16 rq{s_ring[0], s_qhead[0], s_qtail[0], (uint32_t)kRing - 1u};
@@ -1015,14 +963,11 @@ __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArg
     const bool walker = (int)(threadIdx.x >> 6) < RS::walkers;
     if (walker) {
         // ---- walker wave ----
-        using LdsAnc = __attribute__((address_space(3))) AncT;
-        LdsAnc* anc = S && (!RT_ANC16 || sc.n_pid <= 0x10000) ? (LdsAnc*)s_anc + threadIdx.x : nullptr;
+        LdsAncU16* anc = S && sc.n_pid <= 0x10000 ? (LdsAncU16*)s_anc + threadIdx.x : nullptr;
         int32_t q = -1;
         bool closest = false;
         WalkRegs r;
-#if RT_ROLES_PRIO
-        __builtin_amdgcn_s_setprio(RT_ROLES_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(1);  // walker waves at raised issue priority (their dependent loads issue first)
         for (;;) {
             RT_DBG_TSTART(t_wi);
             const int idle = __popcll(__ballot(q < 0));
@@ -1065,7 +1010,7 @@ __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArg
                 if (!fin && r.w.cur >= 0) {
                     double t;
                     int prim;
-                    const int st = walk_step<S, RS::walk_threads, C::phong ? 0 : RT_WALK_HOIST>(sc, sc.meshes[r.mi], r.wr, r.wi,
+                    const int st = walk_step<S, RS::walk_threads, C::phong ? 0 : 1>(sc, sc.meshes[r.mi], r.wr, r.wi,
                                                                                              r.w, &t, &prim, anc);
                     if (st != WALK_RUN) {
                         if (closest) {
@@ -1105,9 +1050,7 @@ __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArg
             if (fin) q = -1;
             RT_DBG_TEND(4, t_wi);
         }
-#if RT_ROLES_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
     } else {
         // ---- shader wave ----
         int32_t p = -1;
@@ -1245,14 +1188,14 @@ __device__ __forceinline__ void roles_body(const DevScene& sc_g, const RenderArg
 template <int F, int W, bool S, int B = RoleShape<Cfg<F>>::block>
 __global__ __launch_bounds__(B, W) void k_megakernel_roles_f64(DevScene sc_g, RenderArgs a_g, double* __restrict__ sub_buf,
                                                                 uint32_t* next_sub, long nsub) {
-    roles_body<F, S, B, kFrame>(sc_g, a_g, sub_buf, next_sub, nsub, nullptr);
+    roles_body<F, S, B, kFrame>(sub_buf, next_sub, nsub, nullptr);
 }
 // The pixel-list instance: nsub = 4 n_pixels units, sub_buf the compact [n_pixels][4][3] buffer.
 template <int F, int W, bool S, int B = RoleShape<Cfg<F>>::block>
 __global__ __launch_bounds__(B, W) void k_megakernel_roles_list_f64(DevScene sc_g, RenderArgs a_g,
                                                                      double* __restrict__ sub_buf, uint32_t* next_sub,
                                                                      long nsub, const uint32_t* __restrict__ pixels) {
-    roles_body<F, S, B, kList>(sc_g, a_g, sub_buf, next_sub, nsub, pixels);
+    roles_body<F, S, B, kList>(sub_buf, next_sub, nsub, pixels);
 }
 // The batched-passes instance: nsub = 4 n_units units, units[u] = pixel | pass << 28 (pass < 16),
 // seeds[16] on the device, sub_buf the compact [n_units][4][3] buffer. Scheduling is the list instance's.
@@ -1261,7 +1204,7 @@ __global__ __launch_bounds__(B, W) void k_megakernel_roles_passes_f64(DevScene s
                                                                        double* __restrict__ sub_buf, uint32_t* next_sub,
                                                                        long nsub, const uint32_t* __restrict__ units,
                                                                        const uint64_t* __restrict__ seeds) {
-    roles_body<F, S, B, kPasses>(sc_g, a_g, sub_buf, next_sub, nsub, units, seeds);
+    roles_body<F, S, B, kPasses>(sub_buf, next_sub, nsub, units, seeds);
 }
 
 // One launch of the role-split pool, its split tail planned and summed: a frame (L = kFrame), a pixel list (kList:
@@ -1383,7 +1326,7 @@ RT_DEV bool diag_slots_meshes(const DevScene& sc, const Ray& r, const RayInv& in
         if (!next_mesh_walk_near<C, true>(sc, r, inv, tmax, g, mi, w, near)) break;
         double t;
         int prim, st;
-        while ((st = walk_step<true, 256, RT_WALK_HOIST>(sc, sc.meshes[mi], r, inv, w, &t, &prim, anc)) == WALK_RUN) {
+        while ((st = walk_step<true, 256, 1>(sc, sc.meshes[mi], r, inv, w, &t, &prim, anc)) == WALK_RUN) {
         }
         if (st == WALK_HIT) {
             if (vis) occluded = !(t + 0.001 >= dist);  // mutually_visible's ERR_MARGIN
@@ -1436,7 +1379,7 @@ __global__ __launch_bounds__(256) void k_diag_slots(DevScene sc, DiagArgs a, int
 // iff a hit has !(t + 0.001 >= dist), and defer.c is added iff none occludes.
 template <int F, bool kSink>
 __global__ __launch_bounds__(256) void k_diag_vertex_slots(DevScene sc, RenderArgs a, DiagVertexArgs v) {
-    using C = Cfg<F | (RT_OPT_LDSOBJ ? kCfgLdsObj : 0) | kCfgTabUse>;  // as the pools
+    using C = Cfg<F | kCfgLdsObj | kCfgTabUse>;  // as the pools
     if constexpr (C::ldsobj) lds_objects_fill(sc);
     __shared__ int32_t s_anc[kSlotAncLevels * 256];
     LdsAncI32* anc = (LdsAncI32*)s_anc + threadIdx.x;

@@ -6,8 +6,9 @@ family does and add ShadowDefer::c iff no mesh occludes), on the batteries of te
 conditions tests/test_vertex_states.py checks on the CPU). No statistical allowance: every vertex of every family is
 compared.
 
-The reference is the oracle's variant 1 (oracle.cpp vertex_step): the device's algebraic forms (RT_OPT_NEE, RT_OPT_BETA,
-RT_OPT_LEF / RT_OPT_KPI, the cancelled MIS weights) written in plain IEEE C++ with glibc's libm. Both sides are built
+The reference is the oracle's variant 1 (oracle.cpp vertex_step): the device's algebraic forms (shade_vertex's NEE term
+through one reciprocal and its continuation weight as k / p, the host-evaluated DevObject::lef and brdf_eval's
+DevObject::kpi, the cancelled MIS weights) written in plain IEEE C++ with glibc's libm. Both sides are built
 without floating-point contraction (-ffp-contract=off in raytracer-server_amd/Makefile's COMMON flags for every f64
 kernel file, and in oracle/Makefile), so with equal libm results the device must produce variant 1's bits.
 
@@ -23,7 +24,7 @@ Numeric (L, beta, the next direction, pdf_prev), per vertex and per output:
 where a nudge moves glibc's sin and cos (and, in scenes with a Phong object, the specular lobe's two pow results) by
 -1 / 0 / +1 ulp: the factor 2 because the device's trig is claimed within 1 ulp of glibc, itself up to an ulp from the
 true value; the 2 ulp term for norm() of a nudged vector. Where no libm call feeds an output (mirror and camera
-vertices, beta under RT_OPT_BETA, the whole of a mesh light's NEE) the envelope is zero and the comparison is bit for
+vertices, beta as shade_vertex's k / p, the whole of a mesh light's NEE) the envelope is zero and the comparison is bit for
 bit up to the 2 ulp term. Nothing in the bound is measured on the device.
 
 Each battery is submitted twice, in family order and under a fixed permutation, both padded to a size that is no

@@ -15,7 +15,7 @@ from conftest import REPO
 LLVM = "/opt/rocm/lib/llvm/bin"
 LIB = os.path.join(REPO, "raytracer-server_amd", "lib", "librtamd.so")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-# kernels whose bodies call karg_scene() / karg_render_args() (RT_KARG_VIEW), by mangled-name stem
+# kernels whose bodies call karg_scene() / karg_render_args() (megakernel_common.h), by mangled-name stem
 VIEW_KERNELS = ("k_megakernel_f64", "k_megakernel_mesh_f64", "k_megakernel_roles_f64", "k_megakernel_fpool_f64",
                 "k_render_list_f64", "k_megakernel_roles_list_f64", "k_megakernel_fpool_list_f64", "k_selftest_tables")
 # superseded kernels compiled only into the A/B build (ab_knobs.h: lib/variants/ab.so)
