@@ -38,7 +38,7 @@ struct SubPixel {
     int col, yref, sx, sy, sub;
 };
 RT_DEV SubPixel subpixel_of(const RenderArgs& a, long p) {
-    const uint32_t pix = (uint32_t)(p >> 2);  // < width * height < 2^32 (rt_api.cpp: check_params)
+    const uint32_t pix = (uint32_t)(p >> 2);  // < width * height < 2^32 (api/common.cpp: check_params)
     const uint32_t tw = (uint32_t)a.tw;
     const uint32_t r = pix / tw;
     SubPixel s;

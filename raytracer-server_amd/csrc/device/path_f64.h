@@ -661,7 +661,7 @@ RT_DEV void walk_enter_mask(const Ray& ray, const RayInv& inv, OctWalk& w, uint3
 // conservative near_box cull). tmax: see near_box.
 // Slots: the walk continues with walk_step<true> (the slot walk: the root is entered in its first step),
 // or with walk_step<false> (the node_kids walk: entered here). The slot walk needs DevScene::node_slot
-// (absent for octrees whose node ids do not fit a KidSlot entry: rt_api.cpp pack_scene).
+// (absent for octrees whose node ids do not fit a KidSlot entry: scene_pack.cpp pack_scene).
 // cull = false: the caller already knows the ray passes near_box for this mesh (mesh_near_mask).
 template <bool Slots = (RT_WALK_TIGHT != 0)>
 RT_DEV bool walk_begin(const DevScene& sc, const DevMesh& m, const Ray& ray, const RayInv& inv, double tmax,
@@ -793,7 +793,7 @@ RT_DEV int leaf_tris_loaded(const Ray& ray, OctWalk& w, const DevTri* tr, const 
 // subtree's triangle bounds: the same conservative slab test as near_box. Skipping such a child leaves
 // the walk's result unchanged: the reference would descend, test every triangle below it, find none,
 // and go on with the next child in visiting order.
-// The bound codes decode as base + q * step: rt_api.cpp make_slot keeps the scene's slot tables only when no
+// The bound codes decode as base + q * step: scene_pack.cpp make_slot keeps the scene's slot tables only when no
 // code was clamped to the 16-bit range, so every decoded bound encloses its subtree's padded triangle bounds.
 RT_DEV double tight_bound(uint32_t q, double step, double base) { return fma((double)q, step, base); }
 // The slab test's final comparison with its 1e-9 relative padding: the padding applied once, to
@@ -1958,7 +1958,7 @@ RT_DEV void light_sample(const DevScene& sc, Rng& rng, V3* y, V3* ny, double* pd
         V3 n = norm<C::g1>(v3(x, yy, z));
         *y = ld3(L.pos) + n * L.r;
         *ny = n;
-        *pdf = sc.light_pdf;  // 1.0 / (4.0 * PI * L.r * L.r), same bits (host, rt_api.cpp: upload)
+        *pdf = sc.light_pdf;  // 1.0 / (4.0 * PI * L.r * L.r), same bits (host, api/scene.cpp: upload)
         return;
     }
     // mesh light: area-weighted pick + Triangle::sample with the reference's missing `+ a`

@@ -69,7 +69,7 @@ struct alignas(16) DevMesh {
 };
 constexpr int kFlatMaxTris = 32;
 constexpr int kFlatMeshes = 2;  // meshes of a flat scene: the flat kernels' LDS queues and result columns
-                                // (render_flat_f64.hip) and rt_api.cpp's RenderArgs::all_flat
+                                // (render_flat_f64.hip) and make_render_args' RenderArgs::all_flat
 
 // BVH over a mesh's triangles for the nearest-triangle mode (RT_FLAG_MESH_NEAREST), nodes in DFS
 // pre-order: an inner node's left child is the next node, `a` its right child, `axis` the split
@@ -94,7 +94,7 @@ RT_LAYOUT_FN int32_t kid_leaf(int32_t leaf, int32_t first, int32_t count) {
 // with the parent encoding below) and the child subtree's triangle
 // bounds ("tight box": the vertices of every triangle in the subtree's leaves, padded by
 // DevMesh::cull_pad), rounded OUTWARD to 16-bit codes over the mesh's range (DevMesh::tight_base /
-// tight_step: bound = base + q * step, one extra step each way (rt_api.cpp make_slot: no code is clamped, or the
+// tight_step: bound = base + q * step, one extra step each way (scene_pack.cpp make_slot: no code is clamped, or the
 // scene has no slot tables; before round 5 a low code 0 meant -inf, a high code
 // 65535 +inf). Triangles may reach far outside their octant (geometry.rs:1038-1060 assigns any
 // triangle that touches it), so the bounds are not the octant box. A ray that passes farther than the

@@ -1,4 +1,4 @@
-// Progressive accumulation: launchers of accum.hip, called by rt_api.cpp (rt_accum_*).
+// Progressive accumulation: launchers of accum.hip, called by the api units (rt_accum_*).
 #pragma once
 
 #include <hip/hip_runtime.h>

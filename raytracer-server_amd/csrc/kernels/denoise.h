@@ -1,5 +1,5 @@
 // Denoised previews: first-hit feature buffers and the edge-avoiding a-trous filter.
-// Launchers of denoise.hip, called by rt_api.cpp (rt_render_features*, rt_denoise*).
+// Launchers of denoise.hip, called by api/denoise.cpp (rt_render_features*, rt_denoise*).
 #pragma once
 
 #include <hip/hip_runtime.h>

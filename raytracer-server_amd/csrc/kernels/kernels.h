@@ -1,4 +1,4 @@
-// Host-visible launchers of the HIP kernels (implemented in *.hip, called by rt_api.cpp).
+// Host-visible launchers of the HIP kernels (implemented in *.hip, called by the csrc/api units).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,7 +54,7 @@ extern thread_local TailPlan t_tail_plan;
 // profiles/r06u_ab_tail.log) -> 1909.1 (2; 2.5: 1910.7, profiles/r06y_ab_tail_n8.log) Msamples/s; full frames at
 // 0.5 -> 1.5 per lane: cornell 1988.3 -> 2003.8 (2: 2001.2, profiles/r06ai_ab_tail_full.log), cubes 1079.5 -> 1085.5,
 // N = 2 shares cornell 1963.9 -> 1987.8 and cubes 1067.5 -> 1079.7 (profiles/r06aj_ab_tail_full.log).
-// rt_api.cpp sizes the split-tail scratch with the same rule.
+// ensure_tail_scratch (api/render.cpp) sizes the split-tail scratch with the same rule.
 inline int tail_split_x2(long nsub, long lanes) { return nsub <= 4 * lanes ? 4 : 3; }
 // Split-tail scratch bytes per split subpixel (megakernel_common.h plan_tail: the samples after chunk 0).
 size_t tail_scratch_per_subpixel(int n_samples);

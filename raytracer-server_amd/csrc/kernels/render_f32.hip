@@ -19,7 +19,7 @@
 // (wave-aggregated tickets); object loops over the scalar-loaded compact tables (Compact32);
 // camera samples computed ahead into an LDS buffer in whole-wave passes.
 // Supported: diffuse and mirror BRDFs, sphere lights, spheres / planes / meshes, MIS on or off —
-// every reference scene. Phong and mesh lights are rejected on the host (rt_api.cpp).
+// every reference scene. Phong and mesh lights are rejected on the host (render_enqueue).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -103,7 +103,7 @@ __device__ __forceinline__ void fused_body(double* __restrict__ sub_buf, uint32_
     // tickets: whole subpixels, then the split tail's chunks (unit_of)
     const long n_split = nsub - a.n_whole;
     const long nunits = a.n_wunits + n_split * a.tail_cps;
-    int id, s;  // subpixel (tile-local, < 2^31: rt_api.cpp check_params) and sample of the unit in hand
+    int id, s;  // subpixel (tile-local, < 2^31: api/common.cpp check_params) and sample of the unit in hand
     const long t0 = wave_ticket(next_sub, true);
     {
         int end_unused;  // the run's end is recomputed when needed (run_end)
@@ -649,7 +649,7 @@ hipError_t launch_megakernel_f64(const DevScene& sc, const RenderArgs& a_in, dou
 // instance of a.features & 15, with the frame's Cfg choice, mesh instances at 3 waves/SIMD and analytic ones at
 // RT_MK_W4, handed out in runs of whole units (plan_units, no split tail); kListFpool / kListRoles: the list or passes
 // instances of the scene's pool kernel, planned as its frame is (split tail included). RT_FLAG_FP32 and
-// RT_FLAG_MESH_NEAREST are out of scope (rt_api.cpp returns RT_E_INVAL).
+// RT_FLAG_MESH_NEAREST are out of scope (check_render_pixels returns RT_E_INVAL).
 hipError_t launch_render_units_f64(const DevScene& sc, const RenderArgs& a_in, const UnitList& units, double* sub_buf,
                                    uint32_t* next_unit, int family, double* tail_buf, size_t tail_cap, hipStream_t st) {
     if (units.n <= 0 || a_in.n_samples <= 0) return hipSuccess;

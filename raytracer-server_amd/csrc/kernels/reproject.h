@@ -1,5 +1,5 @@
 // Accumulator reprojection across camera moves: the launcher of reproject.hip, called by
-// rt_api.cpp (rt_accum_reproject). The definition, operation by operation, is in include/rt_ffi.h;
+// api/accum.cpp (rt_accum_reproject). The definition, operation by operation, is in include/rt_ffi.h;
 // tests/reproject_ref.py restates it.
 #pragma once
 

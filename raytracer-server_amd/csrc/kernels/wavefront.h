@@ -52,7 +52,7 @@ struct Workspace {
     size_t tail_cap = 0;
     uint32_t* host_ctrl = nullptr;  // pinned mirror of ctrl
     hipEvent_t ev = nullptr;
-    // Pool bookkeeping (rt_api.cpp: take_workspace / give_workspace): `busy` is recorded on the
+    // Pool bookkeeping (api/render.cpp: take_workspace / give_workspace): `busy` is recorded on the
     // render's stream after its last launch; the workspace is handed to another render only once
     // that event has completed, or to a render on the same stream (ordered after it anyway).
     hipEvent_t busy = nullptr;
